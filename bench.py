@@ -6,6 +6,7 @@ whole batch), plus -- with more than one GPU -- an RCCL all_gather of every
 rank's per-runtime packet counts and rx counters over xGMI.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+                    [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 Rank 0 prints one JSON line.  Workload (configs[1] of BASELINE.json): 32 Mi
@@ -13,9 +14,14 @@ synthetic 64-B Eth/IPv4/UDP frames per GPU, uniform 5-tuples, 16 runtimes x 8
 kthreads, JENKINS flow hash; packets are sharded round-robin across ranks in
 64 Ki-packet blocks.  --scaling weak (default) keeps 32 Mi packets per GPU;
 --scaling strong splits SURVEY §8(e)'s 256 Mi-packet batch (config 4) over
-the ranks.  At N=1 the secondary config (1500-B TCP, Zipf-0.99 flows, 1024
-runtimes), the integrated ingress-pool shape and the CPU baseline (the
+the ranks.
+
+A plain run sets up, warms up, times the K steps and prints the line.  With
+--full, at N=1 the layout's ceiling, the gcl_group rows, the secondary config
+(1500-B TCP, Zipf-0.99 flows, 1024 runtimes), the integrated ingress-pool
+shape, the host-memory and rx_burst pipeline rows and the CPU baseline (the
 oracle's restatement of rx.c on this host's cores) are added.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import json
@@ -576,13 +582,14 @@ SETTLE_MS = float(os.environ.get("GCL_BENCH_SETTLE_MS", "30"))
 WINDOW_MS = float(os.environ.get("GCL_BENCH_WINDOW_MS", "10"))
 
 
-def run_timed(w, steps, warmup, world, ex=None):
+def run_timed(w, steps, warmup, world, ex=None, before_last=None):
     """Warm up, then time exactly `steps` steps between a barrier +
     synchronize on both sides.  Returns (wall seconds, max over ranks;
     GPU ms per step, max over ranks): the second is a HIP event pair on the
     launch stream around the timed steps, so it is the classify kernels'
     back-to-back time (launch gaps included) and never exceeds the wall
-    time of a step."""
+    time of a step.  `before_last` (--dump-outputs) is called on the launch
+    stream just before the last timed step."""
     stream = torch.cuda.current_stream()
 
     def one():
@@ -628,7 +635,9 @@ def run_timed(w, steps, warmup, world, ex=None):
     e1 = torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     e0.record(stream)
-    for _ in range(steps):
+    for k in range(steps):
+        if before_last is not None and k == steps - 1:
+            before_last()
         one()
     if ex is not None:
         ex.drain()
@@ -1786,6 +1795,41 @@ def spawn_ranks(n, argv, timeout_s=SPAWN_TIMEOUT_S):
     return 0
 
 
+# --dump-outputs: at most this many float32 values of the verdict ring are
+# written (32 MiB; the counts and counters beside it are a few hundred bytes)
+DUMP_MAX_VALUES = 8 << 20
+
+
+def sample_verdicts(raw, n, vbytes, max_values=DUMP_MAX_VALUES):
+    """The [n, vbytes] verdict bytes in @raw (a uint8 array) as float32: all
+    of them when they fit @max_values, else the verdicts of a fixed sample
+    of packets (indices drawn with replacement from a generator seeded with
+    SEED, so every run with the same arguments picks the same packets)."""
+    v = np.asarray(raw, dtype=np.uint8)[:n * vbytes].reshape(n, vbytes)
+    k = max(1, max_values // vbytes)
+    if n > k:
+        v = v[np.random.default_rng(SEED).integers(0, n, size=k)]
+    return v.astype(np.float32)
+
+
+def dump_outputs(path, w, rank, world, counts_before_last=None):
+    """What the last timed step handed its caller, as @path/<name>.npy: the
+    verdict ring (sample_verdicts; one file per rank) and, where the step
+    counts into the workload's own vector (no exchange), that step's
+    per-runtime packet counts and rx counters: the vector after the step
+    less its copy taken on the stream just before it."""
+    os.makedirs(path, exist_ok=True)
+    nbytes = w.n * w.vbytes
+    hv = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+    hip_copy(hv, w.verdicts, nbytes)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(path, f"verdicts{suffix}.npy"), sample_verdicts(hv.numpy(), w.n, w.vbytes))
+    if counts_before_last is not None:
+        last = (w.counts - counts_before_last).cpu().numpy().astype(np.float64)
+        np.save(os.path.join(path, f"counts{suffix}.npy"), last[:w.R])
+        np.save(os.path.join(path, f"stats{suffix}.npy"), last[w.R:])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1796,11 +1840,21 @@ def main():
                     help="weak: 32 Mi packets per GPU; strong: --total-pkts split over the ranks")
     ap.add_argument("--total-pkts", type=int, default=STRONG_TOTAL_PKTS,
                     help="strong scaling: packets per step over all ranks (default 256 Mi)")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the layout's ceiling (gcl_access_probe), the gcl_group rows, "
+                         "the other verdict widths, hash modes and workloads, the host-memory and rx_burst "
+                         "pipeline rows and the CPU baseline (each can be dropped with its --no-* option); "
+                         "at N>1 also the kernel-only steps, e2e_multi, group_node and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy: "
+                         "verdicts (float32 [packets, verdict bytes], a fixed seeded sample of the packets "
+                         "when the ring is larger than 32 MiB of float32) and, without an exchange, counts "
+                         "and stats (float64: that step's per-runtime packet counts and rx counters)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary rows")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the host-memory rows")
     ap.add_argument("--no-group", action="store_true",
-                    help="skip the gcl_group (C ABI + RCCL) lines at N=1")
+                    help="with --full: skip the gcl_group (C ABI + RCCL) lines at N=1")
     ap.add_argument("--group-node-force", action="store_true",
                     help="run the group_node line (gcl_group over the line's N GPUs) even at N=1")
     ap.add_argument("--group-child", type=int, default=0, help=argparse.SUPPRESS)
@@ -1852,8 +1906,16 @@ def main():
         n_rank = args.total_pkts // world
     w = Workload(args.workload, rank, world, device, vbytes=vb, n=n_rank)
     ex = Exchange(w, world, device, args.exchange_every) if dist_on else None
-    el, gms = run_timed(w, args.steps, args.warmup, world, ex)
+    before_last = counts_before_last = None
+    if args.dump_outputs and ex is None:
+        counts_before_last = torch.empty_like(w.counts)
+
+        def before_last():
+            counts_before_last.copy_(w.counts)
+    el, gms = run_timed(w, args.steps, args.warmup, world, ex, before_last)
     settle_steps = run_timed.last_settle
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, w, rank, world, counts_before_last)
     total_pkts = w.n * world * args.steps
     value = total_pkts / el / 1e6
     # correctness spot check: every packet of every step was accounted for
@@ -1865,11 +1927,14 @@ def main():
         expect = w.n * (args.steps + args.warmup + settle_steps)
     counts_ok = tot == expect
     # kernel-only next to the exchange-inclusive step: the same
-    # steps without the all_gather, barrier + max-over-ranks timed
-    if ex is not None:
+    # steps without the all_gather, barrier + max-over-ranks timed (a run of
+    # its own: --full)
+    if ex is None:
+        el_k, gms_k = el, gms
+    elif args.full:
         el_k, gms_k = run_timed(w, args.steps, 2, world, None)
     else:
-        el_k, gms_k = el, gms
+        el_k = gms_k = None
     w_n = w.n
     scaling_desc = (f"weak: {w.n} pkts per GPU" if args.scaling == "weak" else
                     f"strong: {args.total_pkts} pkts per step over {world} GPU(s), {w.n} per GPU")
@@ -1893,25 +1958,29 @@ def main():
                    "parallelism": (f"dp{world}: round-robin 64Ki-pkt shards, {args.dist_backend} "
                                    f"all_gather of per-runtime counts every {args.exchange_every} step(s), overlapped"
                                    if dist_on else "single GPU")},
-        "roofline": {**roofline(w, gms_k),
-                     **ceiling(w.clf, w.frames, w.n, w.stride, w.verdicts, gms_k)},
-        "kernel_only": {
-            "value": round(w_n * world * args.steps / el_k / 1e6, 1), "unit": "Mpkt/s",
-            "ms_per_step": round(el_k / args.steps * 1e3, 4), "gpu_ms_per_step": round(gms_k, 4),
-            "what": ("the same classify steps without the counts all_gather, barrier + "
-                     "max-over-ranks timed" if ex is not None else
-                     "N=1 without an exchange: the step is the classify launch")},
         "placement": placement(w),
         "counts_check": "ok" if counts_ok else f"MISMATCH {tot} != {expect}",
         "settle": {"steps": settle_steps, "ms_target": SETTLE_MS,
                    "what": ("untimed steps after the warmup, so the timed steps start after "
                             ">= ms_target of continuous launches (DESIGN.md §5)")},
     }
+    if gms_k is not None:
+        # the roofline of the timed steps' own launch time; the layout's
+        # ceiling beside it takes launches of its own (--full)
+        result["roofline"] = roofline(w, gms_k)
+        if args.full:
+            result["roofline"].update(ceiling(w.clf, w.frames, w.n, w.stride, w.verdicts, gms_k))
+        result["kernel_only"] = {
+            "value": round(w_n * world * args.steps / el_k / 1e6, 1), "unit": "Mpkt/s",
+            "ms_per_step": round(el_k / args.steps * 1e3, 4), "gpu_ms_per_step": round(gms_k, 4),
+            "what": ("the same classify steps without the counts all_gather, barrier + "
+                     "max-over-ranks timed" if ex is not None else
+                     "N=1 without an exchange: the step is the classify launch")}
     if ex is not None:
         result["exchange"] = {"gpu_ms_per_step": round(gms, 4), "period_steps": args.exchange_every,
                               "periods": ex.k, "backend": torch.distributed.get_backend(),
                               "ranks": torch.distributed.get_world_size()}
-    if world == 1 and not args.no_group:
+    if world == 1 and args.full and not args.no_group:
         try:
             result["group"] = group_bench(w, args.steps, args.warmup, dev_index, args.exchange_every,
                                           settle=settle_steps)
@@ -1919,13 +1988,13 @@ def main():
             result["group"] = {"error": str(e)}
     del w, ex
     torch.cuda.empty_cache()
-    if world == 1 and not args.no_group:
+    if world == 1 and args.full and not args.no_group:
         node = group_node_line(args, 1)
         if node is not None:
             result["group_node"] = node
     torch.cuda.empty_cache()
 
-    if world == 1 and not args.no_secondary and args.workload == "udp64" and args.scaling == "weak":
+    if world == 1 and args.full and not args.no_secondary and args.workload == "udp64" and args.scaling == "weak":
         # the same udp64 step with the other verdict formats
         other = []
         for ob in (b for b in (8, 4, 2, 1) if b != vb):
@@ -1981,10 +2050,10 @@ def main():
                                "header_split_layout": hsplit, "udp64_other_verdicts": other,
                                "udp64_toeplitz": toeplitz}
 
-    if world == 1 and not args.no_e2e and args.workload == "udp64" and args.scaling == "weak":
+    if world == 1 and args.full and not args.no_e2e and args.workload == "udp64" and args.scaling == "weak":
         result["e2e"] = e2e_bench(device, vb)
 
-    if world == 1 and not args.no_cpu:
+    if world == 1 and args.full and not args.no_cpu:
         cpu = cpu_baseline(args.cpu_budget)
         cpu["gpu_over_1core_nic"] = round(value / cpu["value"], 1)
         result["cpu_baseline"] = cpu
@@ -1996,11 +2065,11 @@ def main():
                                                        c3["jenkins_mode"]["1core_mpps"], 1)}
         if "e2e" in result:
             result["e2e"]["mixed"]["cpu_baseline"] = cpu["streams"]["mixed"]
-    if world > 1 and not args.no_e2e:
+    if world > 1 and args.full and not args.no_e2e:
         result["e2e_multi"] = e2e_multi(device, rank, world, vb)
     if dist_on:
         shard.finish()  # every rank's GPU work done (barrier), the process group gone
-    if world > 1 and rank == 0:
+    if world > 1 and args.full and rank == 0:
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
         result.update(node_extras(args, world, value))

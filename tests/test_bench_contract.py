@@ -349,3 +349,21 @@ def test_cpu_child_runs_without_gpu():
     cpu = json.loads(lines[0])
     assert cpu["value"] > 0 and cpu["cores"] == 1 and cpu["kind"] == "port"
     assert cpu["nic_mode"]["1core_lrpc_mpps"] > 0 and "tcp1500" in cpu["streams"]
+
+
+def test_sample_verdicts_whole_or_fixed_sample(bench):
+    """--dump-outputs: a ring that fits is written whole, a larger one as the
+    verdicts of the same seeded packets in every run, float32 either way."""
+    import numpy as np
+    n, vb = 1000, 2
+    raw = (np.arange(n * vb + 7) % 251).astype(np.uint8)  # a ring longer than n verdicts
+    whole = bench.sample_verdicts(raw, n, vb, max_values=n * vb)
+    assert whole.dtype == np.float32 and whole.shape == (n, vb)
+    assert (whole == raw[:n * vb].reshape(n, vb)).all()
+    a = bench.sample_verdicts(raw, n, vb, max_values=100)
+    b = bench.sample_verdicts(raw, n, vb, max_values=100)
+    assert a.shape == (50, vb) and a.dtype == np.float32 and (a == b).all()
+    idx = np.random.default_rng(bench.SEED).integers(0, n, size=50)
+    assert (a == raw[:n * vb].reshape(n, vb)[idx]).all()
+    # the headline ring (32 Mi x 1 B) as sampled stays far below 64 MB
+    assert bench.DUMP_MAX_VALUES * 4 <= 32 << 20
