@@ -364,7 +364,10 @@ struct gcl_verdict4 gcl_verdict1_to4(uint8_t v, uint8_t thread_bits)
  * order, so the outcome is the same packet by packet.  A write prefetch of
  * the ring slot 8-32 packets ahead made it slower (profiles/archive/r01_deliver.txt).
  * Verdicts are @v2 (2-byte, of a context with @thread_bits), @v1 (1-byte) or
- * @v4; always inlined with constant NULLs for the two absent forms. */
+ * @v4; always inlined with constant NULLs for the two absent forms.  @idx,
+ * when not NULL, lists the packets to take (gcl_host_deliver_idx): packet j
+ * of the pass is idx[j], which indexes every per-packet array and is what
+ * the callbacks see. */
 static inline __attribute__((always_inline)) uint64_t
 deliver_compact(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtimes,
                 struct gcl_host_proc *const *clients, int nr_clients,
@@ -372,7 +375,8 @@ deliver_compact(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtime
                 uint8_t thread_bits,
                 const uint32_t *bcast_hash, const uint16_t *pkt_len, const uint8_t *olflags,
                 uint8_t default_olflags, const uint64_t *shmptr, uint64_t n,
-                const struct gcl_host_ops *ops, uint64_t *stats, size_t vstride)
+                const struct gcl_host_ops *ops, uint64_t *stats, size_t vstride,
+                const uint32_t *idx)
 {
 	const uint64_t csum_def = (default_olflags & GCL_F_IP_CKSUM_MASK) == GCL_F_IP_CKSUM_GOOD;
 	void (*const enable_poll)(void *, struct gcl_host_proc *, unsigned int) =
@@ -381,7 +385,9 @@ deliver_compact(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtime
 	const uint32_t tmask = (1u << thread_bits) - 1;
 	uint64_t delivered = 0;
 
-	for (uint64_t i = 0; i < n; i++) {
+	for (uint64_t j = 0; j < n; j++) {
+		/* packet j of the pass: j itself, or the plan list's entry */
+		const uint64_t i = idx ? idx[j] : j;
 		struct gcl_host_proc *p;
 		struct gcl_lrpc_chan_out *chan;
 		uint32_t uniqid, slot, th;
@@ -447,7 +453,7 @@ uint64_t gcl_host_deliver4(struct gcl_host_proc *const *clients_by_id, uint32_t 
 {
 	return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, v, NULL, NULL, 0,
 	                       bcast_hash, pkt_len, olflags, default_olflags, shmptr, n, ops, stats,
-	                       sizeof(*v));
+	                       sizeof(*v), NULL);
 }
 
 uint64_t gcl_host_deliver2(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtimes,
@@ -461,7 +467,7 @@ uint64_t gcl_host_deliver2(struct gcl_host_proc *const *clients_by_id, uint32_t 
 		return 0;
 	return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, NULL, v, NULL,
 	                       thread_bits, bcast_hash, pkt_len, olflags, default_olflags, shmptr,
-	                       n, ops, stats, sizeof(*v));
+	                       n, ops, stats, sizeof(*v), NULL);
 }
 
 uint64_t gcl_host_deliver1(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtimes,
@@ -475,7 +481,7 @@ uint64_t gcl_host_deliver1(struct gcl_host_proc *const *clients_by_id, uint32_t 
 		return 0;
 	return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, NULL, NULL, v,
 	                       thread_bits, bcast_hash, pkt_len, olflags, default_olflags, shmptr,
-	                       n, ops, stats, sizeof(*v));
+	                       n, ops, stats, sizeof(*v), NULL);
 }
 
 void gcl_host_prefetch_rxq(struct gcl_host_proc *const *clients, int nr_clients)
@@ -511,19 +517,19 @@ uint64_t gcl_host_deliver_recs(struct gcl_host_proc *const *clients_by_id, uint3
 		return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients,
 		                       (const struct gcl_verdict4 *)&recs[0].verdict, NULL, NULL, 0,
 		                       bcast_hash, pkt_len, olflags, default_olflags, shmptr, n, ops, stats,
-		                       sizeof(*recs));
+		                       sizeof(*recs), NULL);
 	if (vbytes == 2)
 		return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, NULL,
 		                       (const uint16_t *)&recs[0].verdict, NULL, thread_bits, bcast_hash,
 		                       pkt_len, olflags, default_olflags, shmptr, n, ops, stats,
-		                       sizeof(*recs));
+		                       sizeof(*recs), NULL);
 	if (vbytes == 1)
 		return thread_bits > 7 ? 0
 		                       : deliver_compact(clients_by_id, max_runtimes, clients, nr_clients,
 		                                         NULL, NULL, (const uint8_t *)&recs[0].verdict,
 		                                         thread_bits, bcast_hash, pkt_len, olflags,
 		                                         default_olflags, shmptr, n, ops, stats,
-		                                         sizeof(*recs));
+		                                         sizeof(*recs), NULL);
 	if (vbytes != 8)
 		return 0;
 	/* 8-byte contexts: a record's first 8 bytes are the struct gcl_verdict */
@@ -531,6 +537,47 @@ uint64_t gcl_host_deliver_recs(struct gcl_host_proc *const *clients_by_id, uint3
 		struct gcl_verdict v;
 		memcpy(&v, &recs[i], sizeof(v));
 		delivered += deliver(clients_by_id, max_runtimes, clients, nr_clients, &v, NULL, NULL,
+		                     pkt_len ? pkt_len + i : NULL, olflags ? olflags + i : NULL,
+		                     default_olflags, shmptr ? shmptr + i : NULL, 1, ops, i, stats);
+	}
+	return delivered;
+}
+
+/* The post-pass over a delivery plan's list (gcl_plan): the packets
+ * @idx[0..m) in list order, each through the same per-packet body as the
+ * in-order passes above (deliver_compact, or deliver for 8-byte verdicts). */
+uint64_t gcl_host_deliver_idx(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtimes,
+                              struct gcl_host_proc *const *clients, int nr_clients,
+                              const void *v, uint8_t vbytes, uint8_t thread_bits,
+                              const uint32_t *bcast_hash, const uint16_t *pkt_len,
+                              const uint8_t *olflags, uint8_t default_olflags,
+                              const uint64_t *shmptr, const uint32_t *idx, uint64_t m,
+                              const struct gcl_host_ops *ops, uint64_t *stats)
+{
+	uint64_t delivered = 0;
+
+	if (!v || !idx || thread_bits > 8)
+		return 0;
+	if (vbytes == 4)
+		return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, v, NULL, NULL, 0,
+		                       bcast_hash, pkt_len, olflags, default_olflags, shmptr, m, ops, stats,
+		                       sizeof(struct gcl_verdict4), idx);
+	if (vbytes == 2)
+		return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, NULL, v, NULL,
+		                       thread_bits, bcast_hash, pkt_len, olflags, default_olflags, shmptr,
+		                       m, ops, stats, sizeof(uint16_t), idx);
+	if (vbytes == 1)
+		return thread_bits > 7 ? 0
+		                       : deliver_compact(clients_by_id, max_runtimes, clients, nr_clients,
+		                                         NULL, NULL, v, thread_bits, bcast_hash, pkt_len,
+		                                         olflags, default_olflags, shmptr, m, ops, stats,
+		                                         sizeof(uint8_t), idx);
+	if (vbytes != 8)
+		return 0;
+	for (uint64_t j = 0; j < m; j++) {
+		const uint64_t i = idx[j];
+		delivered += deliver(clients_by_id, max_runtimes, clients, nr_clients,
+		                     (const struct gcl_verdict *)v + i, NULL, NULL,
 		                     pkt_len ? pkt_len + i : NULL, olflags ? olflags + i : NULL,
 		                     default_olflags, shmptr ? shmptr + i : NULL, 1, ops, i, stats);
 	}

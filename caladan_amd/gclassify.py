@@ -191,6 +191,19 @@ class GclHostOps(ctypes.Structure):
                 ("arp_respond", ARP_RESPOND_FN)]
 
 
+PLAN_BY_RUNTIME = 0  # a packet-index list per runtime (every verdict width)
+PLAN_BY_QUEUE = 1    # ... per flow-table queue (1- and 2-byte verdicts)
+
+
+class GclPlanCfg(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("key", ctypes.c_uint32), ("blocks", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+
+class GclPlanOut(ctypes.Structure):
+    _fields_ = [("order", ctypes.c_void_p), ("bucket_off", ctypes.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} missing: run `python caladan_amd/build.py` "
@@ -251,6 +264,13 @@ def _load():
         "gcl_host_deliver_recs": (u64, [vp, u32, vp, i32, vp, ctypes.c_uint8, ctypes.c_uint8, vp, vp,
                                         vp, ctypes.c_uint8, vp, u64, ctypes.POINTER(GclHostOps), vp]),
         "gcl_host_prefetch_rxq": (None, [vp, i32]),
+        "gcl_host_deliver_idx": (u64, [vp, u32, vp, i32, vp, ctypes.c_uint8, ctypes.c_uint8, vp, vp,
+                                       vp, ctypes.c_uint8, vp, vp, u64, ctypes.POINTER(GclHostOps), vp]),
+        "gcl_plan_buckets": (i32, [vp, u32, ctypes.POINTER(u32)]),
+        "gcl_plan_workspace": (i32, [vp, ctypes.POINTER(GclPlanCfg), u64,
+                                     ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_plan": (i32, [vp, ctypes.POINTER(GclPlanCfg), vp, u64, ctypes.POINTER(GclPlanOut), vp,
+                           ctypes.c_size_t, vp]),
         "gcl_rxloop_peek": (i32, [vp, ctypes.c_int64, u64, ctypes.POINTER(vp), ctypes.POINTER(u32)]),
         "gcl_rxloop_release": (i32, [vp, ctypes.c_int64]),
         "gcl_rxloop_poll_stats": (i32, [vp, vp]),
@@ -629,6 +649,43 @@ class Classifier:
         o = GclE2eOpts(mode=mode, nstreams=nstreams, chunk=chunk)
         return _check(lib.gcl_classify_host(self._ctx, ctypes.byref(b), _ptr(verdicts), _ptr(counts),
                                             _ptr(stats), ctypes.byref(o)), "gcl_classify_host")
+
+    def plan_buckets(self, key=PLAN_BY_RUNTIME):
+        """gcl_plan_buckets: the plan's bucket count, the host bucket included."""
+        nb = ctypes.c_uint32()
+        _check(lib.gcl_plan_buckets(self._ctx, key, ctypes.byref(nb)), "gcl_plan_buckets")
+        return nb.value
+
+    def plan(self, verdicts, n, key=PLAN_BY_RUNTIME, order=None, bucket_off=None, blocks=0,
+             stream=None):
+        """gcl_plan: the stable partition of @n classified packets by runtime
+        (or queue), asynchronous.  Returns (order, bucket_off): u32[n] packet
+        indices and u32[nbuckets + 1] list starts (given as int32 tensors when
+        allocated here).  The scratch is a torch tensor kept on the classifier
+        and reused while it is large enough."""
+        import torch
+        nb = self.plan_buckets(key)
+        if _nbytes(verdicts) < self.vbytes * n:
+            raise ValueError("verdict buffer too small")
+        dev = verdicts.device if hasattr(verdicts, "device") else None
+        if order is None:
+            order = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        if bucket_off is None:
+            bucket_off = torch.empty(nb + 1, dtype=torch.int32, device=dev)
+        if _nbytes(order) < 4 * n or _nbytes(bucket_off) < 4 * (nb + 1):
+            raise ValueError("plan output buffer too small")
+        cfg = GclPlanCfg(size=ctypes.sizeof(GclPlanCfg), key=key, blocks=blocks)
+        need = ctypes.c_size_t()
+        _check(lib.gcl_plan_workspace(self._ctx, ctypes.byref(cfg), n, ctypes.byref(need)),
+               "gcl_plan_workspace")
+        ws = getattr(self, "_plan_ws", None)
+        if ws is None or ws.numel() < need.value or ws.device != order.device:
+            ws = self._plan_ws = torch.empty(max(need.value, 16), dtype=torch.uint8,
+                                             device=order.device)
+        out = GclPlanOut(order=_ptr(order), bucket_off=_ptr(bucket_off))
+        _check(lib.gcl_plan(self._ctx, ctypes.byref(cfg), _ptr(verdicts), n, ctypes.byref(out),
+                            _ptr(ws), ws.numel(), stream), "gcl_plan")
+        return order, bucket_off
 
     def rxloop(self, region, slots=64, max_burst=GCL_RX_BURST_SIZE, workers=1, lifetime_ms=20000,
                counts=None, stats=None, region_len=None, flags=0):

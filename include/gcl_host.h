@@ -163,6 +163,39 @@ uint64_t gcl_host_deliver_recs(struct gcl_host_proc *const *clients_by_id, uint3
                                const struct gcl_host_ops *ops, uint64_t *stats);
 
 /*
+ * gcl_host_deliver_idx - the same post-pass over the packets @idx[0..m) of a
+ * batch, in list order: one list of a delivery plan (gcl_plan, gclassify.h).
+ * @v is the batch's whole verdict array in the context's width @vbytes (1, 2,
+ * 4 or 8; @thread_bits as gcl_host_deliver2 / 1); every per-packet array
+ * (@v, @bcast_hash, @pkt_len, @olflags, @shmptr) is indexed by idx[j], and
+ * every callback is given idx[j].  The per-packet work is that of
+ * gcl_host_deliver{,4,2,1}.  Returns 0 for a bad @vbytes / @thread_bits.
+ *
+ * Guarantee: delivering the per-runtime lists of a GCL_PLAN_BY_RUNTIME plan
+ * one after another (in any order of runtimes, from any cores, as long as one
+ * runtime's list is delivered by one core) puts the same message sequence
+ * into every kthread ring as gcl_host_deliver* does over the whole batch,
+ * with the same counters in sum -- provided no callback during the batch
+ * changes ANOTHER runtime's flow_tbl or active_thread_count: inside one
+ * runtime's list the packet order is the batch's, and a runtime's steering
+ * depends on nothing else.  A sched_add_core that preempts another runtime to
+ * find a core (sched.c:208-216) is outside the guarantee.  The lists of a
+ * GCL_PLAN_BY_QUEUE plan keep the order within a queue only.  The host bucket
+ * (BROADCAST, ARP_RESPOND, drops) touches every client's rings: it is
+ * delivered by whichever core owns dp.clients, and never while another core
+ * delivers (rings are single-producer); an Azure ARP broadcast's messages
+ * then sit before or after the batch's unicast messages instead of between
+ * them.
+ */
+uint64_t gcl_host_deliver_idx(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtimes,
+                              struct gcl_host_proc *const *clients, int nr_clients,
+                              const void *v, uint8_t vbytes, uint8_t thread_bits,
+                              const uint32_t *bcast_hash, const uint16_t *pkt_len,
+                              const uint8_t *olflags, uint8_t default_olflags,
+                              const uint64_t *shmptr, const uint32_t *idx, uint64_t m,
+                              const struct gcl_host_ops *ops, uint64_t *stats);
+
+/*
  * gcl_host_prefetch_rxq - a hint for a dataplane thread with time to spare
  * (waiting for a burst's verdicts): the ring slot each kthread's next message
  * lands in, and the channel state, taken for writing, so that the post-pass

@@ -8,7 +8,9 @@
  * 349-363), and steer the packet to a runtime kthread through that runtime's
  * flow table (rx_send_to_runtime, iokernel/rx.c:50-73).  The GPU emits one
  * 8-byte verdict per packet; the host (one dataplane thread, as in the
- * reference) turns verdicts into lrpc_send() calls (see gcl_host.h).
+ * reference) turns verdicts into lrpc_send() calls (see gcl_host.h); gcl_plan
+ * (below) partitions a classified batch by runtime on the GPU, so that
+ * several host cores can each deliver their own runtimes' packets.
  *
  * Conventions follow the reference: every function returns 0 or -errno
  * (rx_init iokernel/rx.c:398-415, lrpc_init_out base/lrpc.c:38-52), nothing is
@@ -745,6 +747,71 @@ int gcl_rxloop_stamps(struct gcl_rxloop *loop, int64_t ticket, uint64_t out[8]);
 int gcl_rxloop_stop(struct gcl_rxloop *loop);
 int gcl_rxloop_drive(struct gcl_rxloop *loop, uint32_t n, const uint64_t *offs, uint32_t iters,
                      uint32_t depth, uint64_t *lat_ns, uint64_t *elapsed_ns);
+
+/*
+ * Delivery plan: a stable partition of a classified batch by destination, on
+ * the GPU.  The host post-pass walks a verdict array in packet order on one
+ * core; a plan gives it one packet-index list per runtime (or per flow-table
+ * queue) instead, each in ascending packet order, so that disjoint sets of
+ * runtimes can be delivered by different cores with gcl_host_deliver_idx
+ * (gcl_host.h) and every kthread ring still receives the message sequence it
+ * receives from one in-order pass.  The per-bucket counts let a core check
+ * ring space before it starts.
+ *
+ * @verdicts is a device array in the context's own width (8, 4, 2 or 1 B), as
+ * gcl_classify wrote it, 16-B aligned.  The last bucket, the host bucket,
+ * takes every packet that is not DELIVER or WAKE (DROP_*, BROADCAST,
+ * ARP_RESPOND), and every verdict whose key would be >= nbuckets - 1 (a
+ * uniqid >= max_runtimes, the undefined 2-B kind 0x8000, garbage): no byte
+ * pattern in @verdicts indexes outside the counters or outside order[0, n).
+ *  GCL_PLAN_BY_RUNTIME  nbuckets = max_runtimes + 1; the key is the uniqid
+ *                       (8-/4-B), or the queue index >> thread_bits (2-/1-B)
+ *  GCL_PLAN_BY_QUEUE    nbuckets = (max_runtimes << thread_bits) + 1; the key
+ *                       is the queue index q of a 2-/1-B verdict; -EINVAL on
+ *                       an 8-/4-B context
+ * Result: bucket_off[b] is the number of packets with key < b,
+ * bucket_off[nbuckets] = n, and order[bucket_off[b] .. bucket_off[b + 1]) the
+ * indices of bucket b's packets, ascending: order is the stable argsort of
+ * the keys.
+ *
+ * gcl_plan_buckets   - nbuckets of @key for this context.
+ * gcl_plan_workspace - bytes of device scratch a plan of @n verdicts takes
+ *                      (the counters of every packet range: ranges x nbuckets
+ *                      x 4 B, at most 16 MiB by the library's own choice of
+ *                      ranges, plus the scan's block sums).
+ * gcl_plan           - asynchronous on @hip_stream; no host synchronisation
+ *                      and no allocation.  @workspace (device, 16-B aligned)
+ *                      need not be zeroed and may be reused by the next call
+ *                      on the same stream.  @verdicts must not change between
+ *                      the call and its completion: the kernels read them
+ *                      twice (a caller who breaks this gets a wrong list, never
+ *                      a write outside order[0, n)).  n == 0 zeroes
+ *                      bucket_off.  -EINVAL for a bad size or key, NULL or
+ *                      misaligned pointers, n > 2^31, a workspace that is too
+ *                      small, BY_QUEUE on a wide-verdict context, or
+ *                      blocks x nbuckets > 2^24; -EIO when a launch fails.
+ */
+enum gcl_plan_key {
+	GCL_PLAN_BY_RUNTIME = 0, /* every verdict width */
+	GCL_PLAN_BY_QUEUE   = 1, /* GCL_CFG_VERDICT1 / VERDICT2 contexts only */
+};
+struct gcl_plan_cfg {
+	uint32_t size;    /* sizeof(struct gcl_plan_cfg) */
+	uint32_t key;     /* enum gcl_plan_key */
+	uint32_t blocks;  /* 0: the library's choice; else the number of contiguous
+	                     packet ranges the batch is cut into (tests) */
+	uint32_t pad;
+};
+struct gcl_plan_out {
+	uint32_t *order;      /* device u32[n] */
+	uint32_t *bucket_off; /* device u32[nbuckets + 1] */
+};
+int gcl_plan_buckets(const struct gcl_ctx *ctx, uint32_t key, uint32_t *nbuckets);
+int gcl_plan_workspace(const struct gcl_ctx *ctx, const struct gcl_plan_cfg *cfg, uint64_t n,
+                       size_t *bytes);
+int gcl_plan(struct gcl_ctx *ctx, const struct gcl_plan_cfg *cfg, const void *verdicts, uint64_t n,
+             const struct gcl_plan_out *out, void *workspace, size_t workspace_bytes,
+             void *hip_stream);
 
 /* Library version string. */
 const char *gcl_version(void);
