@@ -237,6 +237,63 @@ static bool send_to_runtime(struct gcl_host_proc *p, uint32_t hash, int slot,
 	return gcl_lrpc_send(p->rxq[th], cmd, payload);
 }
 
+/* One packet of the post-pass, rx_one_pkt's exits after classification
+ * (rx.c:171-233): the verdict's fields, the broadcast @hash, the ready
+ * message {@cmd, @payload}, and the packet index @i the callbacks see.
+ * Returns 1 when the packet was handed to a runtime. */
+static uint64_t deliver_one(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtimes,
+                            struct gcl_host_proc *const *clients, int nr_clients,
+                            uint16_t uniqid, uint8_t thread, uint8_t act, uint32_t hash,
+                            uint64_t cmd, unsigned long payload,
+                            const struct gcl_host_ops *ops, uint64_t i, uint64_t *stats)
+{
+	struct gcl_host_proc *p = NULL;
+
+	if (act == GCL_ACT_DELIVER || act == GCL_ACT_WAKE) {
+		if (uniqid < max_runtimes)
+			p = clients_by_id[uniqid];
+		if (p && send_to_runtime(p, hash, (int)thread, cmd, payload, ops)) {
+			if (ops && ops->owned)
+				ops->owned(ops->arg, p, i);
+			return 1;
+		}
+		stats[GCL_RX_UNICAST_FAIL]++; /* rx.c:140-142, :213-215 */
+	} else if (act == GCL_ACT_BROADCAST) {
+		int n_sent = 0;
+		for (int c = 0; c < nr_clients; c++) {
+			if (send_to_runtime(clients[c], hash, -1, cmd, payload, ops)) {
+				n_sent++;
+				if (ops && ops->owned)
+					ops->owned(ops->arg, clients[c], i);
+			} else {
+				stats[GCL_RX_BROADCAST_FAIL]++;
+			}
+		}
+		if (n_sent == 0) {
+			if (ops && ops->free_pkt)
+				ops->free_pkt(ops->arg, i);
+			return 0;
+		}
+		if (ops && ops->refcnt_update)
+			ops->refcnt_update(ops->arg, i, n_sent - 1);
+		return 1; /* rx.c:185-189: no RX_UNHANDLED */
+	} else if (act == GCL_ACT_ARP_RESPOND) {
+		if (ops && ops->arp_respond && ops->arp_respond(ops->arg, i))
+			return 0;
+		stats[GCL_RX_UNREGISTERED_MAC]++; /* rx.c:205 */
+	} else {
+		/* DROP_*: the device already counted them */
+		if (ops && ops->free_pkt)
+			ops->free_pkt(ops->arg, i);
+		return 0;
+	}
+	/* fail_free, rx.c:225-232 */
+	if (ops && ops->free_pkt)
+		ops->free_pkt(ops->arg, i);
+	stats[GCL_RX_UNHANDLED]++;
+	return 0;
+}
+
 /* One verdict stream, either format: @v8 (gcl_verdict) or @v4 (gcl_verdict4,
  * whose broadcast hashes come from @bcast_hash).  Callbacks see packet
  * index @base + i. */
@@ -256,56 +313,10 @@ static uint64_t deliver(struct gcl_host_proc *const *clients_by_id, uint32_t max
 		const uint8_t act = (v8 ? v8[i].action : v4[i].action) & GCL_ACT_MASK;
 		const uint32_t hash = v8 ? v8[i].hash : (bcast_hash ? bcast_hash[i] : 0);
 		uint8_t fl = olflags ? olflags[i] : default_olflags;
-		uint64_t cmd = gcl_rx_make_cmd(pkt_len ? pkt_len[i] : 0, fl);
-		unsigned long payload = shmptr ? shmptr[i] : 0;
-		struct gcl_host_proc *p = NULL;
-		bool ok;
 
-		if (act == GCL_ACT_DELIVER || act == GCL_ACT_WAKE) {
-			if (uniqid < max_runtimes)
-				p = clients_by_id[uniqid];
-			ok = p && send_to_runtime(p, hash, (int)thread, cmd, payload, ops);
-			if (ok) {
-				delivered++;
-				if (ops && ops->owned)
-					ops->owned(ops->arg, p, base + i);
-				continue;
-			}
-			stats[GCL_RX_UNICAST_FAIL]++; /* rx.c:140-142, :213-215 */
-		} else if (act == GCL_ACT_BROADCAST) {
-			int n_sent = 0;
-			for (int c = 0; c < nr_clients; c++) {
-				if (send_to_runtime(clients[c], hash, -1, cmd, payload, ops)) {
-					n_sent++;
-					if (ops && ops->owned)
-						ops->owned(ops->arg, clients[c], base + i);
-				} else {
-					stats[GCL_RX_BROADCAST_FAIL]++;
-				}
-			}
-			if (n_sent == 0) {
-				if (ops && ops->free_pkt)
-					ops->free_pkt(ops->arg, base + i);
-			} else {
-				delivered++;
-				if (ops && ops->refcnt_update)
-					ops->refcnt_update(ops->arg, base + i, n_sent - 1);
-			}
-			continue; /* rx.c:185-189: no RX_UNHANDLED */
-		} else if (act == GCL_ACT_ARP_RESPOND) {
-			if (ops && ops->arp_respond && ops->arp_respond(ops->arg, base + i))
-				continue;
-			stats[GCL_RX_UNREGISTERED_MAC]++; /* rx.c:205 */
-		} else {
-			/* DROP_*: the device already counted them */
-			if (ops && ops->free_pkt)
-				ops->free_pkt(ops->arg, base + i);
-			continue;
-		}
-		/* fail_free, rx.c:225-232 */
-		if (ops && ops->free_pkt)
-			ops->free_pkt(ops->arg, base + i);
-		stats[GCL_RX_UNHANDLED]++;
+		delivered += deliver_one(clients_by_id, max_runtimes, clients, nr_clients, uniqid, thread,
+		                         act, hash, gcl_rx_make_cmd(pkt_len ? pkt_len[i] : 0, fl),
+		                         shmptr ? shmptr[i] : 0, ops, base + i, stats);
 	}
 	return delivered;
 }
@@ -354,20 +365,30 @@ struct gcl_verdict4 gcl_verdict1_to4(uint8_t v, uint8_t thread_bits)
 	return o;
 }
 
+/* the packed records of a list (gcl_plan_pack), as deliver_compact takes them */
+struct packed_recs {
+	const uint64_t *cmd, *payload; /* [m], in list order */
+	uint64_t n;                    /* packets in the batch */
+};
+
 /* deliver() for compact verdicts, with the common case inlined: a DELIVER
  * verdict for a runtime that still has an active kthread goes straight into
  * the ring of flow_tbl[slot] as it stands now (rx.c:55-59, then :76-92),
  * with the two per-delivery callbacks of the reference,
  * thread_enable_sched_poll and the ownership record.  Everything else (WAKE,
  * a runtime whose last core a scheduler side effect of this batch took,
- * broadcast, drops, a full ring) takes deliver() for that one packet, in
+ * broadcast, drops, a full ring) takes deliver_one() for that one packet, in
  * order, so the outcome is the same packet by packet.  A write prefetch of
  * the ring slot 8-32 packets ahead made it slower (profiles/archive/r01_deliver.txt).
  * Verdicts are @v2 (2-byte, of a context with @thread_bits), @v1 (1-byte) or
  * @v4; always inlined with constant NULLs for the two absent forms.  @idx,
  * when not NULL, lists the packets to take (gcl_host_deliver_idx): packet j
  * of the pass is idx[j], which indexes every per-packet array and is what
- * the callbacks see. */
+ * the callbacks see.  @pk, when not NULL, holds the list's packed records
+ * (gcl_host_deliver_packed): verdict (@v4) and message of packet j of the
+ * pass are read at position j, idx[j] only names the packet to the
+ * callbacks and indexes @bcast_hash, and an idx[j] outside the batch is
+ * skipped. */
 static inline __attribute__((always_inline)) uint64_t
 deliver_compact(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtimes,
                 struct gcl_host_proc *const *clients, int nr_clients,
@@ -376,7 +397,7 @@ deliver_compact(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtime
                 const uint32_t *bcast_hash, const uint16_t *pkt_len, const uint8_t *olflags,
                 uint8_t default_olflags, const uint64_t *shmptr, uint64_t n,
                 const struct gcl_host_ops *ops, uint64_t *stats, size_t vstride,
-                const uint32_t *idx)
+                const uint32_t *idx, const struct packed_recs *pk)
 {
 	const uint64_t csum_def = (default_olflags & GCL_F_IP_CKSUM_MASK) == GCL_F_IP_CKSUM_GOOD;
 	void (*const enable_poll)(void *, struct gcl_host_proc *, unsigned int) =
@@ -393,12 +414,16 @@ deliver_compact(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtime
 		uint32_t uniqid, slot, th;
 		bool fast;
 
+		if (pk && i >= pk->n)
+			continue; /* names no packet: no callback, no counter */
 		/* verdict i sits @vstride bytes after verdict i - 1: packed
-		 * arrays, or the rx loop's 16-B records read in place */
-		const uint16_t *v2i = v2 ? (const uint16_t *)((const char *)v2 + i * vstride) : NULL;
-		const uint8_t *v1i = v1 ? (const uint8_t *)v1 + i * vstride : NULL;
+		 * arrays, or the rx loop's 16-B records read in place; a list's
+		 * packed records hold the verdict of idx[j] at j */
+		const uint64_t vi = pk ? j : i;
+		const uint16_t *v2i = v2 ? (const uint16_t *)((const char *)v2 + vi * vstride) : NULL;
+		const uint8_t *v1i = v1 ? (const uint8_t *)v1 + vi * vstride : NULL;
 		const struct gcl_verdict4 *v4i =
-			v4 ? (const struct gcl_verdict4 *)((const char *)v4 + i * vstride) : NULL;
+			v4 ? (const struct gcl_verdict4 *)((const char *)v4 + vi * vstride) : NULL;
 		if (v1) { /* no WAKE mark: the active count below decides, as rx.c:59 */
 			const uint8_t x = *v1i;
 			uniqid = (x & GCL_V1_Q_MASK) >> thread_bits;
@@ -421,21 +446,28 @@ deliver_compact(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtime
 		    chan->send_head - chan->send_tail >= chan->size) {
 			const struct gcl_verdict4 w = v1 ? gcl_verdict1_to4(*v1i, thread_bits)
 			                            : v2 ? gcl_verdict2_to4(*v2i, thread_bits) : *v4i;
-			delivered += deliver(clients_by_id, max_runtimes, clients, nr_clients, NULL, &w,
-			                     bcast_hash ? bcast_hash + i : NULL, pkt_len ? pkt_len + i : NULL,
-			                     olflags ? olflags + i : NULL, default_olflags,
-			                     shmptr ? shmptr + i : NULL, 1, ops, i, stats);
+			const uint64_t cmd = pk ? pk->cmd[j] :
+				gcl_rx_make_cmd(pkt_len ? pkt_len[i] : 0, olflags ? olflags[i] : default_olflags);
+			delivered += deliver_one(clients_by_id, max_runtimes, clients, nr_clients, w.uniqid,
+			                         w.thread, w.action & GCL_ACT_MASK,
+			                         bcast_hash ? bcast_hash[i] : 0, cmd,
+			                         pk ? pk->payload[j] : shmptr ? shmptr[i] : 0, ops, i, stats);
 			continue;
 		}
 		if (enable_poll)
 			enable_poll(ops->arg, p, th);
-		const uint64_t csum = olflags ?
-			(olflags[i] & GCL_F_IP_CKSUM_MASK) == GCL_F_IP_CKSUM_GOOD : csum_def;
+		uint64_t cmd;
+		if (pk) {
+			cmd = pk->cmd[j];
+		} else {
+			const uint64_t csum = olflags ?
+				(olflags[i] & GCL_F_IP_CKSUM_MASK) == GCL_F_IP_CKSUM_GOOD : csum_def;
+			cmd = (uint64_t)(pkt_len ? pkt_len[i] : 0) << 16 | csum << 48;
+		}
 		const uint32_t h = chan->send_head++;
 		struct gcl_lrpc_msg *dst = &chan->tbl[h & (chan->size - 1)];
-		dst->payload = shmptr ? shmptr[i] : 0;
-		__atomic_store_n(&dst->cmd, (uint64_t)(pkt_len ? pkt_len[i] : 0) << 16 | csum << 48 |
-		                            ((h & chan->size) ? 0 : GCL_LRPC_DONE_PARITY),
+		dst->payload = pk ? pk->payload[j] : shmptr ? shmptr[i] : 0;
+		__atomic_store_n(&dst->cmd, cmd | ((h & chan->size) ? 0 : GCL_LRPC_DONE_PARITY),
 		                 __ATOMIC_RELEASE);
 		if (owned)
 			owned(ops->arg, p, i);
@@ -453,7 +485,7 @@ uint64_t gcl_host_deliver4(struct gcl_host_proc *const *clients_by_id, uint32_t 
 {
 	return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, v, NULL, NULL, 0,
 	                       bcast_hash, pkt_len, olflags, default_olflags, shmptr, n, ops, stats,
-	                       sizeof(*v), NULL);
+	                       sizeof(*v), NULL, NULL);
 }
 
 uint64_t gcl_host_deliver2(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtimes,
@@ -467,7 +499,7 @@ uint64_t gcl_host_deliver2(struct gcl_host_proc *const *clients_by_id, uint32_t 
 		return 0;
 	return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, NULL, v, NULL,
 	                       thread_bits, bcast_hash, pkt_len, olflags, default_olflags, shmptr,
-	                       n, ops, stats, sizeof(*v), NULL);
+	                       n, ops, stats, sizeof(*v), NULL, NULL);
 }
 
 uint64_t gcl_host_deliver1(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtimes,
@@ -481,7 +513,7 @@ uint64_t gcl_host_deliver1(struct gcl_host_proc *const *clients_by_id, uint32_t 
 		return 0;
 	return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, NULL, NULL, v,
 	                       thread_bits, bcast_hash, pkt_len, olflags, default_olflags, shmptr,
-	                       n, ops, stats, sizeof(*v), NULL);
+	                       n, ops, stats, sizeof(*v), NULL, NULL);
 }
 
 void gcl_host_prefetch_rxq(struct gcl_host_proc *const *clients, int nr_clients)
@@ -517,19 +549,19 @@ uint64_t gcl_host_deliver_recs(struct gcl_host_proc *const *clients_by_id, uint3
 		return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients,
 		                       (const struct gcl_verdict4 *)&recs[0].verdict, NULL, NULL, 0,
 		                       bcast_hash, pkt_len, olflags, default_olflags, shmptr, n, ops, stats,
-		                       sizeof(*recs), NULL);
+		                       sizeof(*recs), NULL, NULL);
 	if (vbytes == 2)
 		return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, NULL,
 		                       (const uint16_t *)&recs[0].verdict, NULL, thread_bits, bcast_hash,
 		                       pkt_len, olflags, default_olflags, shmptr, n, ops, stats,
-		                       sizeof(*recs), NULL);
+		                       sizeof(*recs), NULL, NULL);
 	if (vbytes == 1)
 		return thread_bits > 7 ? 0
 		                       : deliver_compact(clients_by_id, max_runtimes, clients, nr_clients,
 		                                         NULL, NULL, (const uint8_t *)&recs[0].verdict,
 		                                         thread_bits, bcast_hash, pkt_len, olflags,
 		                                         default_olflags, shmptr, n, ops, stats,
-		                                         sizeof(*recs), NULL);
+		                                         sizeof(*recs), NULL, NULL);
 	if (vbytes != 8)
 		return 0;
 	/* 8-byte contexts: a record's first 8 bytes are the struct gcl_verdict */
@@ -561,17 +593,17 @@ uint64_t gcl_host_deliver_idx(struct gcl_host_proc *const *clients_by_id, uint32
 	if (vbytes == 4)
 		return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, v, NULL, NULL, 0,
 		                       bcast_hash, pkt_len, olflags, default_olflags, shmptr, m, ops, stats,
-		                       sizeof(struct gcl_verdict4), idx);
+		                       sizeof(struct gcl_verdict4), idx, NULL);
 	if (vbytes == 2)
 		return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, NULL, v, NULL,
 		                       thread_bits, bcast_hash, pkt_len, olflags, default_olflags, shmptr,
-		                       m, ops, stats, sizeof(uint16_t), idx);
+		                       m, ops, stats, sizeof(uint16_t), idx, NULL);
 	if (vbytes == 1)
 		return thread_bits > 7 ? 0
 		                       : deliver_compact(clients_by_id, max_runtimes, clients, nr_clients,
 		                                         NULL, NULL, v, thread_bits, bcast_hash, pkt_len,
 		                                         olflags, default_olflags, shmptr, m, ops, stats,
-		                                         sizeof(uint8_t), idx);
+		                                         sizeof(uint8_t), idx, NULL);
 	if (vbytes != 8)
 		return 0;
 	for (uint64_t j = 0; j < m; j++) {
@@ -582,4 +614,21 @@ uint64_t gcl_host_deliver_idx(struct gcl_host_proc *const *clients_by_id, uint32
 		                     default_olflags, shmptr ? shmptr + i : NULL, 1, ops, i, stats);
 	}
 	return delivered;
+}
+
+/* The post-pass over a list's packed records (gcl_plan_pack): deliver_compact
+ * with the verdicts @v4 and the messages read at the list position. */
+uint64_t gcl_host_deliver_packed(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtimes,
+                                 struct gcl_host_proc *const *clients, int nr_clients,
+                                 const uint64_t *cmd, const uint64_t *payload,
+                                 const struct gcl_verdict4 *v4, const uint32_t *idx,
+                                 uint64_t m, uint64_t n, const uint32_t *bcast_hash,
+                                 const struct gcl_host_ops *ops, uint64_t *stats)
+{
+	const struct packed_recs pk = { cmd, payload, n };
+
+	if (!cmd || !payload || !v4 || !idx)
+		return 0;
+	return deliver_compact(clients_by_id, max_runtimes, clients, nr_clients, v4, NULL, NULL, 0,
+	                       bcast_hash, NULL, NULL, 0, NULL, m, ops, stats, sizeof(*v4), idx, &pk);
 }

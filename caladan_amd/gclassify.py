@@ -204,6 +204,17 @@ class GclPlanOut(ctypes.Structure):
     _fields_ = [("order", ctypes.c_void_p), ("bucket_off", ctypes.c_void_p)]
 
 
+class GclPackIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("verdicts", ctypes.c_void_p),
+                ("n", ctypes.c_uint64), ("order", ctypes.c_void_p), ("m", ctypes.c_uint64),
+                ("pkt_len", ctypes.c_void_p), ("olflags", ctypes.c_void_p), ("offs", ctypes.c_void_p),
+                ("stride", ctypes.c_uint64), ("shm_base", ctypes.c_uint64)]
+
+
+class GclPackOut(ctypes.Structure):
+    _fields_ = [("cmd", ctypes.c_void_p), ("payload", ctypes.c_void_p), ("v4", ctypes.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} missing: run `python caladan_amd/build.py` "
@@ -271,6 +282,9 @@ def _load():
                                      ctypes.POINTER(ctypes.c_size_t)]),
         "gcl_plan": (i32, [vp, ctypes.POINTER(GclPlanCfg), vp, u64, ctypes.POINTER(GclPlanOut), vp,
                            ctypes.c_size_t, vp]),
+        "gcl_plan_pack": (i32, [vp, ctypes.POINTER(GclPackIn), ctypes.POINTER(GclPackOut), vp]),
+        "gcl_host_deliver_packed": (u64, [vp, u32, vp, i32, vp, vp, vp, vp, u64, u64, vp,
+                                          ctypes.POINTER(GclHostOps), vp]),
         "gcl_rxloop_peek": (i32, [vp, ctypes.c_int64, u64, ctypes.POINTER(vp), ctypes.POINTER(u32)]),
         "gcl_rxloop_release": (i32, [vp, ctypes.c_int64]),
         "gcl_rxloop_poll_stats": (i32, [vp, vp]),
@@ -686,6 +700,41 @@ class Classifier:
         _check(lib.gcl_plan(self._ctx, ctypes.byref(cfg), _ptr(verdicts), n, ctypes.byref(out),
                             _ptr(ws), ws.numel(), stream), "gcl_plan")
         return order, bucket_off
+
+    def plan_pack(self, verdicts, n, order, m=None, pkt_len=None, olflags=None, offs=None, stride=0,
+                  shm_base=0, out=None, stream=None):
+        """gcl_plan_pack: the ready-to-send records of the list @order[0..m)
+        (a plan's order, or one bucket's slice of it; @m defaults to the whole
+        of @order), asynchronous.  Returns (cmd, payload, v4): u64[m] lrpc
+        commands, u64[m] shm pointers and gcl_verdict4[m], given as int64,
+        int64 and int32 tensors when allocated here; @out is such a triple."""
+        import torch
+        if m is None:
+            if not hasattr(order, "numel"):
+                raise ValueError("m is required when order is a raw address")
+            m = order.numel()
+        if _nbytes(verdicts) < self.vbytes * n:
+            raise ValueError("verdict buffer too small")
+        if _nbytes(order) < 4 * m:
+            raise ValueError("order buffer too small")
+        for arr, w in ((pkt_len, 2), (olflags, 1), (offs, 8)):
+            if arr is not None and _nbytes(arr) < w * n:
+                raise ValueError("per-packet array too small")
+        if out is None:
+            dev = verdicts.device if hasattr(verdicts, "device") else None
+            out = (torch.empty(max(m, 1), dtype=torch.int64, device=dev),
+                   torch.empty(max(m, 1), dtype=torch.int64, device=dev),
+                   torch.empty(max(m, 1), dtype=torch.int32, device=dev))
+        cmd, payload, v4 = out
+        if _nbytes(cmd) < 8 * m or _nbytes(payload) < 8 * m or _nbytes(v4) < 4 * m:
+            raise ValueError("pack output buffer too small")
+        pin = GclPackIn(size=ctypes.sizeof(GclPackIn), verdicts=_ptr(verdicts), n=n, order=_ptr(order),
+                        m=m, pkt_len=_ptr(pkt_len), olflags=_ptr(olflags), offs=_ptr(offs),
+                        stride=stride, shm_base=shm_base)
+        pout = GclPackOut(cmd=_ptr(cmd), payload=_ptr(payload), v4=_ptr(v4))
+        _check(lib.gcl_plan_pack(self._ctx, ctypes.byref(pin), ctypes.byref(pout), stream),
+               "gcl_plan_pack")
+        return cmd, payload, v4
 
     def rxloop(self, region, slots=64, max_burst=GCL_RX_BURST_SIZE, workers=1, lifetime_ms=20000,
                counts=None, stats=None, region_len=None, flags=0):

@@ -196,6 +196,33 @@ uint64_t gcl_host_deliver_idx(struct gcl_host_proc *const *clients_by_id, uint32
                               const struct gcl_host_ops *ops, uint64_t *stats);
 
 /*
+ * gcl_host_deliver_packed - gcl_host_deliver_idx over the same list @idx[0..m)
+ * of a batch of @n packets, fed by the list's packed records (gcl_plan_pack,
+ * gclassify.h) instead of the per-packet arrays: @cmd[j], @payload[j] and
+ * @v4[j] are the message and the widened verdict of packet idx[j], read
+ * sequentially at the list position j.  idx[j] itself is only the packet
+ * number given to the callbacks and the index into @bcast_hash (NULL: hash 0,
+ * as gcl_host_deliver4).  @cmd[j] has bit 63, the ring's parity bit, clear, as
+ * gcl_rx_make_cmd leaves it.  The DELIVER fast path and every other path are
+ * gcl_host_deliver4's.  An entry with idx[j] >= n (gcl_plan_pack gave it the
+ * empty record) is skipped: no callback, no counter.  Returns 0 when @cmd,
+ * @payload, @v4 or @idx is NULL.
+ *
+ * Guarantee: for 4-, 2- and 1-byte contexts every list leaves the ring
+ * messages, callbacks, counters and return value of gcl_host_deliver_idx over
+ * that list, so the guarantee above carries over.  For 8-byte contexts the
+ * same holds for the runtime lists; their host bucket stays with
+ * gcl_host_deliver_idx, because an Azure ARP broadcast fans out by the
+ * verdict's own hash, which the packed records do not carry.
+ */
+uint64_t gcl_host_deliver_packed(struct gcl_host_proc *const *clients_by_id, uint32_t max_runtimes,
+                                 struct gcl_host_proc *const *clients, int nr_clients,
+                                 const uint64_t *cmd, const uint64_t *payload,
+                                 const struct gcl_verdict4 *v4, const uint32_t *idx,
+                                 uint64_t m, uint64_t n, const uint32_t *bcast_hash,
+                                 const struct gcl_host_ops *ops, uint64_t *stats);
+
+/*
  * gcl_host_prefetch_rxq - a hint for a dataplane thread with time to spare
  * (waiting for a burst's verdicts): the ring slot each kthread's next message
  * lands in, and the channel state, taken for writing, so that the post-pass

@@ -813,6 +813,59 @@ int gcl_plan(struct gcl_ctx *ctx, const struct gcl_plan_cfg *cfg, const void *ve
              const struct gcl_plan_out *out, void *workspace, size_t workspace_bytes,
              void *hip_stream);
 
+/*
+ * Packed delivery records: the messages of an index list, ready to send, in
+ * list order.  gcl_host_deliver_idx reads verdicts[idx[j]], pkt_len[idx[j]],
+ * olflags[idx[j]] and shmptr[idx[j]] for every packet of a list: four
+ * dependent reads strided through arrays no core's cache holds.  The GPU
+ * holds the same arrays and gathers them here into three dense ones, which
+ * gcl_host_deliver_packed (gcl_host.h) walks sequentially.  @order is a
+ * plan's order, or one bucket's slice of it (order + bucket_off[b], m =
+ * bucket_off[b + 1] - bucket_off[b]); with i = order[j], for j in [0, m):
+ *   cmd[j]      gcl_rx_make_cmd(pkt_len ? pkt_len[i] : 0,
+ *                               olflags ? olflags[i] : cfg.default_olflags):
+ *               len << 16 | csum_type << 48, bit 63 (the ring's parity) clear
+ *   payload[j]  shm_base + (offs ? offs[i] : i * stride): the frame's
+ *               ptr_to_shmptr (rx.c:82) when the batch's frames lie in the
+ *               ingress region at shm_base
+ *   v4[j]       verdict i as a gcl_verdict4: the last four bytes of an 8-B
+ *               verdict (action flags kept), a 4-B verdict as it is,
+ *               gcl_verdict2_to4 / gcl_verdict1_to4 (gcl_host.h) of a 2- / 1-B
+ *               verdict with the context's thread_bits
+ * An entry order[j] >= n gets cmd = 0, payload = 0 and v4 = {GCL_NO_RUNTIME,
+ * GCL_NO_THREAD, GCL_ACT_MASK}, which gcl_host_deliver_packed skips by its
+ * index: no content of @order or @verdicts causes a read outside [0, n) of a
+ * per-packet array or a write outside [0, m) of the outputs.
+ *
+ * gcl_plan_pack - asynchronous on @hip_stream; no allocation, no host
+ *                 synchronisation; on the same stream it may directly follow
+ *                 the gcl_plan that writes @order.  m == 0 is a no-op.
+ *                 -EINVAL for a wrong size, a NULL verdicts / order / output,
+ *                 an output that is not 16-B aligned, an input that is not
+ *                 aligned to its element (verdicts: the context's width), or
+ *                 m > 2^31; -EIO when the launch fails.
+ */
+struct gcl_pack_in {
+	uint32_t size;            /* sizeof(struct gcl_pack_in) */
+	uint32_t pad;
+	const void     *verdicts; /* device, the context's width, n entries */
+	uint64_t        n;        /* packets in the batch */
+	const uint32_t *order;    /* device u32[m], 4-B aligned */
+	uint64_t        m;        /* entries to pack, <= 2^31 */
+	const uint16_t *pkt_len;  /* optional device u16[n] */
+	const uint8_t  *olflags;  /* optional device u8[n] */
+	const uint64_t *offs;     /* optional device u64[n]; else i * stride */
+	uint64_t        stride;
+	uint64_t        shm_base;
+};
+struct gcl_pack_out {         /* device, 16-B aligned, m entries each */
+	uint64_t *cmd;
+	uint64_t *payload;
+	struct gcl_verdict4 *v4;
+};
+int gcl_plan_pack(struct gcl_ctx *ctx, const struct gcl_pack_in *in,
+                  const struct gcl_pack_out *out, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
