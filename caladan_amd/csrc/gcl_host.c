@@ -200,6 +200,28 @@ uint64_t gcl_rx_make_cmd(uint16_t pkt_len, uint8_t olflags)
 	return 0 /* RX_NET_RECV */ | (uint64_t)pkt_len << 16 | csum << 48;
 }
 
+/* The rule of gcl_rx_csum (gclassify.h) for one frame: a frame that is not
+ * IPv4 or is already IP_CKSUM_GOOD keeps its flags; any other gets the
+ * verdict of chksum_internet over frame bytes [14, 34) (net_rx_one,
+ * runtime/net/core.c:275-279), bytes at or past @len reading 0. */
+uint8_t gcl_rx_csum_flags(const uint8_t *frame, size_t len, uint8_t olflags)
+{
+	uint8_t h[34] = {0};
+	uint32_t sum = 0;
+
+	if (len)
+		memcpy(h, frame, len < sizeof(h) ? len : sizeof(h));
+	if (h[12] != (GCL_ETHTYPE_IP >> 8) || h[13] != (GCL_ETHTYPE_IP & 0xFF) ||
+	    (olflags & GCL_F_IP_CKSUM_MASK) == GCL_F_IP_CKSUM_GOOD)
+		return olflags;
+	for (int i = 14; i < 34; i += 2)
+		sum += h[i] | (uint32_t)h[i + 1] << 8;
+	sum = (sum & 0xFFFF) + (sum >> 16);
+	sum = (sum & 0xFFFF) + (sum >> 16);
+	return (olflags & ~GCL_F_IP_CKSUM_MASK) |
+	       (sum == 0xFFFF ? GCL_F_IP_CKSUM_GOOD : GCL_F_IP_CKSUM_BAD);
+}
+
 /* rx_send_to_runtime (rx.c:50-73) for the flow_tbl slot @slot of runtime @p
  * (hash % thread_count: every DELIVER or WAKE verdict carries it), or, when
  * @slot < 0, the slot of @hash.  The flow_tbl and the active count are read

@@ -46,6 +46,10 @@ NO_RUNTIME, NO_THREAD = 0xFFFF, 0xFF
 (RX_UNREGISTERED_MAC, RX_UNICAST_FAIL, RX_BROADCAST_FAIL, RX_FLOW_TAG_MATCH,
  RX_UNHANDLED, RX_HASH_MISSING, RX_PULLED) = range(7)
 NR_STATS = 8
+# gcl_rx_csum's counter slots
+CSUM_CHECKED, CSUM_GOOD, CSUM_BAD, CSUM_SKIPPED, CSUM_NR = 0, 1, 2, 3, 4
+# its launch (csrc/gcl_csum.hip): packets a block takes per pass, and the grid's cap
+CSUM_BLOCK_PKTS, CSUM_BLOCKS_PER_CU = 256, 7
 STAT_NAMES = ["RX_UNREGISTERED_MAC", "RX_UNICAST_FAIL", "RX_BROADCAST_FAIL",
               "RX_FLOW_TAG_MATCH", "RX_UNHANDLED", "RX_HASH_MISSING", "RX_PULLED"]
 
@@ -283,6 +287,8 @@ def _load():
         "gcl_plan": (i32, [vp, ctypes.POINTER(GclPlanCfg), vp, u64, ctypes.POINTER(GclPlanOut), vp,
                            ctypes.c_size_t, vp]),
         "gcl_plan_pack": (i32, [vp, ctypes.POINTER(GclPackIn), ctypes.POINTER(GclPackOut), vp]),
+        "gcl_rx_csum": (i32, [vp, ctypes.POINTER(GclBatch), vp, vp, vp]),
+        "gcl_rx_csum_flags": (ctypes.c_uint8, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint8]),
         "gcl_host_deliver_packed": (u64, [vp, u32, vp, i32, vp, vp, vp, vp, u64, u64, vp,
                                           ctypes.POINTER(GclHostOps), vp]),
         "gcl_rxloop_peek": (i32, [vp, ctypes.c_int64, u64, ctypes.POINTER(vp), ctypes.POINTER(u32)]),
@@ -376,6 +382,12 @@ def trans_hash(seed, proto, lip, lport, rip, rport):
     t = GclTrans()
     lib.gcl_trans_hash(seed, proto, lip, lport, rip, rport, ctypes.byref(t))
     return t.h5, t.h3
+
+
+def rx_csum_flags(frame: bytes, olflags: int) -> int:
+    """gcl_rx_csum_flags: the rule of Classifier.rx_csum for one frame on the CPU."""
+    frame = bytes(frame)
+    return lib.gcl_rx_csum_flags(frame, len(frame), olflags)
 
 
 def runtime_ip(r: int) -> int:
@@ -735,6 +747,32 @@ class Classifier:
         _check(lib.gcl_plan_pack(self._ctx, ctypes.byref(pin), ctypes.byref(pout), stream),
                "gcl_plan_pack")
         return cmd, payload, v4
+
+    def rx_csum(self, frames, n, stride=0, olflags_out=None, counts=None, offs=None, olflags=None,
+                rss=None, fdir_hi=None, frames_len=None, stream=None, dst_hint=None):
+        """gcl_rx_csum: the batch's ol_flags with the IPv4 header checksum of
+        every packet that is not already IP_CKSUM_GOOD resolved on the GPU
+        (asynchronous).  The batch arguments are classify's (rss, fdir_hi and
+        dst_hint are ignored); @olflags_out may be @olflags (in place) and is
+        allocated as a uint8 tensor when not given; @counts is a device
+        u64[CSUM_NR], accumulated.  Returns the output array."""
+        for arr, w in ((offs, 8), (olflags, 1)):
+            if arr is not None and _nbytes(arr) < w * n:
+                raise ValueError("per-packet array too small")
+        if counts is not None and _nbytes(counts) < 8 * CSUM_NR:
+            raise ValueError("counts buffer too small")
+        if olflags_out is None:
+            import torch
+            dev = frames.device if hasattr(frames, "device") else None
+            olflags_out = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        if _nbytes(olflags_out) < n:
+            raise ValueError("olflags_out buffer too small")
+        b = GclBatch(frames=_ptr(frames), frames_len=_frames_len(frames, frames_len),
+                     stride=stride, offs=_ptr(offs), olflags=_ptr(olflags), rss=None,
+                     fdir_hi=None, pkt_len=None, n=n, dst_hint=None)
+        _check(lib.gcl_rx_csum(self._ctx, ctypes.byref(b), _ptr(olflags_out), _ptr(counts), stream),
+               "gcl_rx_csum")
+        return olflags_out
 
     def rxloop(self, region, slots=64, max_burst=GCL_RX_BURST_SIZE, workers=1, lifetime_ms=20000,
                counts=None, stats=None, region_len=None, flags=0):

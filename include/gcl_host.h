@@ -82,6 +82,18 @@ struct gcl_host_ops {
 uint64_t gcl_rx_make_cmd(uint16_t pkt_len, uint8_t olflags);
 
 /*
+ * gcl_rx_csum_flags - the rule of gcl_rx_csum (gclassify.h) for one frame on
+ * the CPU, for the packets the GPU did not see: the ol_flags of a frame of
+ * @len bytes that arrived with @olflags, its IPv4 header checksum resolved.
+ * Bytes at or past @len read 0 (@frame may be NULL when @len is 0).  A frame
+ * whose bytes 12-13 are not 0x0800, or that is already IP_CKSUM_GOOD, keeps
+ * @olflags; any other gets IP_CKSUM_GOOD when the one's-complement sum of
+ * frame bytes [14, 34) folds to 0xFFFF (chksum_internet returns 0) and
+ * IP_CKSUM_BAD when it does not, every other bit unchanged.
+ */
+uint8_t gcl_rx_csum_flags(const uint8_t *frame, size_t len, uint8_t olflags);
+
+/*
  * gcl_host_deliver - consume @n verdicts in order.
  * @clients_by_id  dp.clients_by_id (iokernel/defs.h:386), @max_runtimes long
  * @clients        dp.clients[0..nr_clients) (broadcast order, rx.c:175)

@@ -866,6 +866,65 @@ struct gcl_pack_out {         /* device, 16-B aligned, m entries each */
 int gcl_plan_pack(struct gcl_ctx *ctx, const struct gcl_pack_in *in,
                   const struct gcl_pack_out *out, void *hip_stream);
 
+/*
+ * IPv4 header checksum offload: the rx offload a NIC reports in
+ * RTE_MBUF_F_RX_IP_CKSUM_*, for batches that arrive without it (a pcap
+ * replay, a NIC or virtual function without the offload, ol_flags that say
+ * UNKNOWN).  rx_make_cmd (iokernel/rx.c:24-38) sends CHECKSUM_TYPE_UNNECESSARY
+ * only for IP_CKSUM_GOOD; for every other packet the receiving runtime runs
+ * chksum_internet(iphdr, sizeof(*iphdr)) itself and drops on a non-zero
+ * result (net_rx_one, runtime/net/core.c:275-279).  gcl_rx_csum makes that
+ * check on the GPU and writes its verdict into the checksum bits of an
+ * ol_flags array, which gcl_host_deliver* and gcl_plan_pack then turn into
+ * cmd as before.
+ *
+ * Packet i, with fl = b->olflags[i], or cfg.default_olflags when b->olflags
+ * is NULL:
+ *   frame bytes 12-13 are not 0x0800        olflags_out[i] = fl    SKIPPED
+ *   fl's checksum bits say IP_CKSUM_GOOD    olflags_out[i] = fl    SKIPPED
+ *   otherwise (UNKNOWN, BAD or NONE)        CHECKED: the one's-complement sum
+ *     of the ten 16-bit words of frame bytes [14, 34) is folded to 16 bits;
+ *     the header is good iff it is 0xFFFF (chksum_internet returns 0), and
+ *     olflags_out[i] = (fl & ~GCL_F_IP_CKSUM_MASK) |
+ *                      (good ? GCL_F_IP_CKSUM_GOOD : GCL_F_IP_CKSUM_BAD),
+ *     counted as GOOD or BAD.
+ *
+ * Guarantee: the reference sends CHECKSUM_TYPE_NEEDED for everything but
+ * IP_CKSUM_GOOD and the runtime then decides by this same 20-byte check, so a
+ * runtime fed gcl_rx_make_cmd(len, olflags_out[i]) accepts exactly the
+ * packets it accepts when fed gcl_rx_make_cmd(len, fl); it only skips the
+ * check on those marked GOOD.  Limit: GOOD here means what net_rx_one
+ * verifies, the first 20 header bytes whatever the IHL says, not a NIC's
+ * whole-header check of a header with options; ip_hdr_supported
+ * (runtime/net/core.c:203-209) drops those frames afterwards either way.
+ *
+ * Frames are addressed as gcl_classify addresses them (frames, frames_len,
+ * stride or offs at any byte alignment; an offset at or past frames_len is a
+ * frame of zeros and every byte at or past frames_len reads 0, so a frame may
+ * be cut anywhere); rss, fdir_hi, dst_hint and pkt_len are ignored.  Every
+ * pointer is a device pointer.  @olflags_out (u8[n]) may be exactly
+ * b->olflags (in place); any other overlap is the caller's error.  @counts is
+ * a device u64[GCL_CSUM_NR], ACCUMULATED, may be NULL; per call CHECKED =
+ * GOOD + BAD and CHECKED + SKIPPED = n.  No content of frames, offs or
+ * olflags causes a read outside frames[0, frames_len), offs[0, n) or
+ * olflags[0, n), or a write outside olflags_out[0, n).
+ *
+ * Asynchronous on @hip_stream; no allocation, no host synchronisation.
+ * n == 0 is a no-op.  -EINVAL for a NULL ctx, b or olflags_out and for the
+ * batches gcl_classify refuses (NULL frames, frames_len == UINT64_MAX,
+ * n > 2^40, a stride < 16, not a multiple of 16 or > 2^20 when offs is NULL);
+ * -EIO when the launch fails.
+ */
+enum {
+	GCL_CSUM_CHECKED = 0, /* packets the check was made for: GOOD + BAD */
+	GCL_CSUM_GOOD,
+	GCL_CSUM_BAD,
+	GCL_CSUM_SKIPPED,     /* not IPv4, or IP_CKSUM_GOOD on entry */
+	GCL_CSUM_NR = 4,
+};
+int gcl_rx_csum(struct gcl_ctx *ctx, const struct gcl_batch *b, uint8_t *olflags_out,
+                uint64_t *counts, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
