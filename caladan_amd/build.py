@@ -24,7 +24,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("GCL_OFFLOAD_ARCH", "gfx950")
 
 SOURCES_HIP = ["gcl_ctx.hip", "gcl_batch.hip", "gcl_loop.hip", "gcl_xfer.hip", "gcl_gen.hip",
-               "gcl_plan.hip", "gcl_pack.hip", "gcl_csum.hip"]
+               "gcl_plan.hip", "gcl_pack.hip", "gcl_csum.hip", "gcl_copy.hip"]
 SOURCES_C = ["gcl_host.c", "gcl_pcap.c"]
 DEPS = ["gcl_device.h", "gcl_kern.h", "gcl_ctx.h", "../../include/gclassify.h", "../../include/gcl_host.h",
         "../../include/gcl_pcap.h"]
@@ -161,11 +161,27 @@ def build_sanitized_csum(out_dir=None):
     return exe
 
 
+def build_sanitized_copy(out_dir=None):
+    """The same ASan + UBSan host build of csrc/gcl_host.c, linked into
+    tests/fuzz/copy_fuzz.c: a stand-alone driver of gcl_copy_batch_host (the
+    loopback frame copy on the CPU) over exactly sized heap regions.  Returns
+    the driver's path."""
+    out_dir = out_dir or os.path.join(ROOT, "build", "sanitize")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "copy_fuzz")
+    srcs = [os.path.join(ROOT, "tests", "fuzz", "copy_fuzz.c"), os.path.join(CSRC, "gcl_host.c")]
+    if _stale(exe, srcs + [os.path.join(CSRC, d) for d in DEPS]):
+        _run(["gcc", "-std=gnu11", "-Wall", "-Wno-unused-parameter", *SANITIZE_FLAGS,
+              "-o", exe, *srcs, "-lm"])
+    return exe
+
+
 if __name__ == "__main__":
     if "--sanitize" in sys.argv:
         print(build_sanitized())
         print(build_sanitized_plan())
         print(build_sanitized_pack())
         print(build_sanitized_csum())
+        print(build_sanitized_copy())
     else:
         build(force="--force" in sys.argv, verbose_resources="--resources" in sys.argv)

@@ -222,6 +222,56 @@ uint8_t gcl_rx_csum_flags(const uint8_t *frame, size_t len, uint8_t olflags)
 	       (sum == 0xFFFF ? GCL_F_IP_CKSUM_GOOD : GCL_F_IP_CKSUM_BAD);
 }
 
+/* The rule of gcl_copy_batch (gclassify.h) on the CPU: copy_batch's loop
+ * (iokernel/dma.c:179-188) with rte_pktmbuf_append's failure made a refusal
+ * and the source bounded by src_len (bytes at or past it read 0). */
+int gcl_copy_batch_host(const struct gcl_copy_in *in, const struct gcl_copy_out *out,
+                        uint64_t *counts)
+{
+	uint64_t copied = 0, refused = 0, bytes = 0;
+
+	if (!in || !out || in->size != sizeof(*in))
+		return -EINVAL;
+	if (in->n == 0)
+		return 0;
+	if (!in->src || !in->src_off || !in->len || !out->dst || !out->pkt_len ||
+	    in->src_len == UINT64_MAX || out->dst_len == UINT64_MAX || in->n > (1ull << 40) ||
+	    (!out->dst_off && (out->dst_stride < 16 || (out->dst_stride & 15) ||
+	                       out->dst_stride > (1u << 20))))
+		return -EINVAL;
+	for (uint64_t i = 0; i < in->n; i++) {
+		const uint64_t len = in->len[i], so = in->src_off[i];
+		const uint64_t d = out->dst_off ? out->dst_off[i] : i * out->dst_stride;
+
+		if (out->olflags)
+			out->olflags[i] = gcl_loopback_olflags(in->tx_olflags ? in->tx_olflags[i] : 0);
+		if (out->rss)
+			out->rss[i] = in->hash ? in->hash[i] : 0;
+		/* rte_pktmbuf_append(dst[i], bytes) */
+		if ((in->dst_cap && len > in->dst_cap) || (!out->dst_off && len > out->dst_stride) ||
+		    d > out->dst_len || len > out->dst_len - d) {
+			out->pkt_len[i] = 0;
+			refused++;
+			continue;
+		}
+		const uint64_t avail = so < in->src_len ? in->src_len - so : 0;
+		const uint64_t have = len < avail ? len : avail;
+		if (have)
+			memcpy(out->dst + d, in->src + so, have);
+		if (len > have)
+			memset(out->dst + d + have, 0, len - have);
+		out->pkt_len[i] = (uint16_t)len;
+		copied++;
+		bytes += len;
+	}
+	if (counts) {
+		counts[GCL_COPY_COPIED] += copied;
+		counts[GCL_COPY_REFUSED] += refused;
+		counts[GCL_COPY_BYTES] += bytes;
+	}
+	return 0;
+}
+
 /* rx_send_to_runtime (rx.c:50-73) for the flow_tbl slot @slot of runtime @p
  * (hash % thread_count: every DELIVER or WAKE verdict carries it), or, when
  * @slot < 0, the slot of @hash.  The flow_tbl and the active count are read

@@ -50,6 +50,10 @@ NR_STATS = 8
 CSUM_CHECKED, CSUM_GOOD, CSUM_BAD, CSUM_SKIPPED, CSUM_NR = 0, 1, 2, 3, 4
 # its launch (csrc/gcl_csum.hip): packets a block takes per pass, and the grid's cap
 CSUM_BLOCK_PKTS, CSUM_BLOCKS_PER_CU = 256, 7
+# gcl_copy_batch's counter slots
+COPY_COPIED, COPY_REFUSED, COPY_BYTES, COPY_NR = 0, 1, 2, 4
+# its launch (csrc/gcl_copy.hip): lanes per block, and the grid's cap
+COPY_THREADS, COPY_BLOCKS_PER_CU = 256, 6
 STAT_NAMES = ["RX_UNREGISTERED_MAC", "RX_UNICAST_FAIL", "RX_BROADCAST_FAIL",
               "RX_FLOW_TAG_MATCH", "RX_UNHANDLED", "RX_HASH_MISSING", "RX_PULLED"]
 
@@ -219,6 +223,19 @@ class GclPackOut(ctypes.Structure):
     _fields_ = [("cmd", ctypes.c_void_p), ("payload", ctypes.c_void_p), ("v4", ctypes.c_void_p)]
 
 
+class GclCopyIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("group", ctypes.c_uint32), ("src", ctypes.c_void_p),
+                ("src_len", ctypes.c_uint64), ("src_off", ctypes.c_void_p), ("len", ctypes.c_void_p),
+                ("tx_olflags", ctypes.c_void_p), ("hash", ctypes.c_void_p), ("n", ctypes.c_uint64),
+                ("len_hint", ctypes.c_uint32), ("dst_cap", ctypes.c_uint32)]
+
+
+class GclCopyOut(ctypes.Structure):
+    _fields_ = [("dst", ctypes.c_void_p), ("dst_len", ctypes.c_uint64), ("dst_off", ctypes.c_void_p),
+                ("dst_stride", ctypes.c_uint64), ("pkt_len", ctypes.c_void_p),
+                ("olflags", ctypes.c_void_p), ("rss", ctypes.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} missing: run `python caladan_amd/build.py` "
@@ -289,6 +306,8 @@ def _load():
         "gcl_plan_pack": (i32, [vp, ctypes.POINTER(GclPackIn), ctypes.POINTER(GclPackOut), vp]),
         "gcl_rx_csum": (i32, [vp, ctypes.POINTER(GclBatch), vp, vp, vp]),
         "gcl_rx_csum_flags": (ctypes.c_uint8, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint8]),
+        "gcl_copy_batch": (i32, [vp, ctypes.POINTER(GclCopyIn), ctypes.POINTER(GclCopyOut), vp, vp]),
+        "gcl_copy_batch_host": (i32, [ctypes.POINTER(GclCopyIn), ctypes.POINTER(GclCopyOut), vp]),
         "gcl_host_deliver_packed": (u64, [vp, u32, vp, i32, vp, vp, vp, vp, u64, u64, vp,
                                           ctypes.POINTER(GclHostOps), vp]),
         "gcl_rxloop_peek": (i32, [vp, ctypes.c_int64, u64, ctypes.POINTER(vp), ctypes.POINTER(u32)]),
@@ -388,6 +407,44 @@ def rx_csum_flags(frame: bytes, olflags: int) -> int:
     """gcl_rx_csum_flags: the rule of Classifier.rx_csum for one frame on the CPU."""
     frame = bytes(frame)
     return lib.gcl_rx_csum_flags(frame, len(frame), olflags)
+
+
+def _copy_structs(src, src_len, src_off, length, tx_olflags, hash, n, len_hint, dst_cap, group,
+                  dst, dst_len, dst_off, dst_stride, pkt_len, olflags, rss):
+    """The two structs of gcl_copy_batch / gcl_copy_batch_host, sizes checked."""
+    for arr, w in ((src_off, 8), (length, 2), (tx_olflags, 1), (hash, 4), (dst_off, 8),
+                   (pkt_len, 2), (olflags, 1), (rss, 4)):
+        if arr is not None and _nbytes(arr) < w * n:
+            raise ValueError("per-packet array too small")
+    cin = GclCopyIn(size=ctypes.sizeof(GclCopyIn), group=group, src=_ptr(src),
+                    src_len=_frames_len(src, src_len), src_off=_ptr(src_off), len=_ptr(length),
+                    tx_olflags=_ptr(tx_olflags), hash=_ptr(hash), n=n, len_hint=len_hint,
+                    dst_cap=dst_cap)
+    cout = GclCopyOut(dst=_ptr(dst), dst_len=_frames_len(dst, dst_len), dst_off=_ptr(dst_off),
+                      dst_stride=dst_stride, pkt_len=_ptr(pkt_len), olflags=_ptr(olflags),
+                      rss=_ptr(rss))
+    return cin, cout
+
+
+def copy_batch_host(src, src_off, length, dst, dst_off=None, dst_stride=0, tx_olflags=None,
+                    hash=None, n=None, src_len=None, dst_len=None, dst_cap=0, counts=None,
+                    pkt_len=None, olflags=None, rss=None):
+    """gcl_copy_batch_host: the rule of Classifier.copy_batch on the CPU over
+    numpy arrays (@dst is written in place).  @pkt_len, @olflags and @rss are
+    allocated when None; False leaves olflags or rss out.  @counts is a
+    u64[COPY_NR], accumulated.  Returns (pkt_len, olflags, rss)."""
+    n = len(length) if n is None else n
+    if pkt_len is None:
+        pkt_len = np.zeros(max(n, 1), dtype=np.uint16)
+    olflags = None if olflags is False else np.zeros(max(n, 1), dtype=np.uint8) if olflags is None else olflags
+    rss = None if rss is False else np.zeros(max(n, 1), dtype=np.uint32) if rss is None else rss
+    if counts is not None and _nbytes(counts) < 8 * COPY_NR:
+        raise ValueError("counts buffer too small")
+    cin, cout = _copy_structs(src, src_len, src_off, length, tx_olflags, hash, n, 0, dst_cap, 0,
+                              dst, dst_len, dst_off, dst_stride, pkt_len, olflags, rss)
+    _check(lib.gcl_copy_batch_host(ctypes.byref(cin), ctypes.byref(cout), _ptr(counts)),
+           "gcl_copy_batch_host")
+    return pkt_len, olflags, rss
 
 
 def runtime_ip(r: int) -> int:
@@ -773,6 +830,33 @@ class Classifier:
         _check(lib.gcl_rx_csum(self._ctx, ctypes.byref(b), _ptr(olflags_out), _ptr(counts), stream),
                "gcl_rx_csum")
         return olflags_out
+
+    def copy_batch(self, src, src_off, length, n, dst, dst_off=None, dst_stride=0, tx_olflags=None,
+                   hash=None, src_len=None, dst_len=None, dst_cap=0, len_hint=0, group=0,
+                   counts=None, pkt_len=None, olflags=None, rss=None, stream=None):
+        """gcl_copy_batch: the loopback frame copy of copy_batch on the GPU
+        (asynchronous): frame i, @length[i] bytes at @src + @src_off[i], into
+        @dst at @dst_off[i] (or i * @dst_stride), refused when it does not fit.
+        @src is a device tensor or a host_register'ed numpy array; @pkt_len
+        (int16), @olflags (uint8) and @rss (int32) are allocated on @dst's
+        device when None; False leaves olflags or rss out.  @counts is a
+        device u64[COPY_NR], accumulated.  Returns (pkt_len, olflags, rss)."""
+        import torch
+        dev = dst.device if hasattr(dst, "device") else None
+        if pkt_len is None:
+            pkt_len = torch.empty(max(n, 1), dtype=torch.int16, device=dev)
+        olflags = None if olflags is False else \
+            torch.empty(max(n, 1), dtype=torch.uint8, device=dev) if olflags is None else olflags
+        rss = None if rss is False else \
+            torch.empty(max(n, 1), dtype=torch.int32, device=dev) if rss is None else rss
+        if counts is not None and _nbytes(counts) < 8 * COPY_NR:
+            raise ValueError("counts buffer too small")
+        cin, cout = _copy_structs(src, src_len, src_off, length, tx_olflags, hash, n, len_hint,
+                                  dst_cap, group, dst, dst_len, dst_off, dst_stride, pkt_len,
+                                  olflags, rss)
+        _check(lib.gcl_copy_batch(self._ctx, ctypes.byref(cin), ctypes.byref(cout), _ptr(counts),
+                                  stream), "gcl_copy_batch")
+        return pkt_len, olflags, rss
 
     def rxloop(self, region, slots=64, max_burst=GCL_RX_BURST_SIZE, workers=1, lifetime_ms=20000,
                counts=None, stats=None, region_len=None, flags=0):

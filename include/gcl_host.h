@@ -94,6 +94,22 @@ uint64_t gcl_rx_make_cmd(uint16_t pkt_len, uint8_t olflags);
 uint8_t gcl_rx_csum_flags(const uint8_t *frame, size_t len, uint8_t olflags);
 
 /*
+ * gcl_copy_batch_host - the rule of gcl_copy_batch (gclassify.h) on the CPU
+ * over host pointers, for the packets the GPU did not see: the copy_batch
+ * loop of iokernel/dma.c:179-188 with the rte_pktmbuf_append check made a
+ * refusal.  @in and @out are gcl_copy_batch's structs with every pointer a
+ * host pointer (in->group and in->len_hint are not looked at); @counts is a
+ * host u64[GCL_COPY_NR],
+ * ACCUMULATED, may be NULL.  The same packets are refused, the same bytes
+ * written and the same guarantee holds.  0, or -EINVAL for a wrong in->size,
+ * a NULL in, out, src, src_off, len, dst or pkt_len, src_len or dst_len ==
+ * UINT64_MAX, n > 2^40, or a dst_stride < 16, not a multiple of 16 or > 2^20
+ * when dst_off is NULL.  n == 0 is a no-op.
+ */
+int gcl_copy_batch_host(const struct gcl_copy_in *in, const struct gcl_copy_out *out,
+                        uint64_t *counts);
+
+/*
  * gcl_host_deliver - consume @n verdicts in order.
  * @clients_by_id  dp.clients_by_id (iokernel/defs.h:386), @max_runtimes long
  * @clients        dp.clients[0..nr_clients) (broadcast order, rx.c:175)

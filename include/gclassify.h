@@ -925,6 +925,100 @@ enum {
 int gcl_rx_csum(struct gcl_ctx *ctx, const struct gcl_batch *b, uint8_t *olflags_out,
                 uint64_t *counts, void *hip_stream);
 
+/*
+ * The loopback frame copy: copy_batch(src_bufs, rx_bufs, n_bufs, rx_one_pkt)
+ * of rx_loopback (iokernel/rx.c:264, iokernel/dma.c:167-191), the step between
+ * the dst_ip lookups (gcl_batch.dst_hint) and rx_one_pkt (gcl_classify).  For
+ * every tx packet the reference appends rte_pktmbuf_pkt_len(src) bytes to a
+ * fresh rx mbuf and copies the frame into it, copies ol_flags, ORs in
+ * RTE_MBUF_F_RX_IP_CKSUM_GOOD and copies hash; where an idxd engine is present
+ * it hands the copy to it (copy_batch_dma, dma.c:140-165).  gcl_copy_batch
+ * makes that copy for a batch on the GPU: @n frames of any length at any byte
+ * alignment out of the tx region into the rx pool that gcl_classify then
+ * reads, with the three per-packet fields the classify batch takes
+ * (gcl_batch.pkt_len is what the post-pass sends, olflags and rss feed
+ * rx_one_pkt).
+ *
+ * Packet i, with L = in->len[i] and d = out->dst_off ? out->dst_off[i] :
+ * i * out->dst_stride:
+ *   REFUSED when in->dst_cap != 0 and L > in->dst_cap, when out->dst_off is
+ *     NULL and L > out->dst_stride, or when the range does not fit the pool:
+ *     d > dst_len or L > dst_len - d (no sum is formed, so any d up to
+ *     UINT64_MAX is judged rightly).  No destination byte is written,
+ *     pkt_len[i] = 0.  This is the rte_pktmbuf_append the reference asserts
+ *     on: a caller drops such a packet (a batch entry with pkt_len 0 is not to
+ *     be classified or delivered) or copies it by other means.
+ *   COPIED otherwise: dst[d + j] = src[src_off[i] + j] for j in [0, L), where
+ *     a source byte at or past src_len reads 0 (src_off[i] + j is never formed
+ *     where it could overflow: an offset at or past src_len is a frame of
+ *     zeros); pkt_len[i] = L; L is added to BYTES.  L == 0 is COPIED and
+ *     writes no byte.
+ *   For every i < n, copied or refused: out->olflags[i] =
+ *     gcl_loopback_olflags(in->tx_olflags ? in->tx_olflags[i] : 0) and
+ *     out->rss[i] = in->hash ? in->hash[i] : 0, each when the output array is
+ *     given.
+ *
+ * @counts is a device u64[GCL_COPY_NR], ACCUMULATED, may be NULL; per call
+ * COPIED + REFUSED = n and BYTES is the sum of pkt_len.
+ *
+ * @src is device-visible memory: HBM, or a tx region registered with
+ * gcl_host_register, given by its host address and read in place over PCIe
+ * (the call looks its device address up; that is a table lookup, no
+ * synchronisation).  Every other pointer is a device pointer.  The u64, u32 and u16 arrays are aligned to their element;
+ * src, dst and the offsets may have any byte alignment.
+ *
+ * Guarantee: no content of src_off, len or dst_off causes a read outside
+ * src[0, src_len) or the n-element input arrays, or a write outside
+ * dst[0, dst_len) or the n-element output arrays; and no destination byte
+ * outside the [d, d + L) of a copied packet is written, not even with the
+ * value it already had: neighbouring mbufs belong to other packets, which
+ * other lanes may be writing at the same time, so there is no
+ * read-modify-write of a wider word.  Two copied packets whose destination
+ * ranges overlap, or any overlap of src and dst, are the caller's error (the
+ * bytes there are then unspecified); nothing is written out of bounds even so.
+ *
+ * in->group = 0 lets the library choose how many lanes copy one packet from
+ * in->len_hint (the typical frame length, 0 = unknown); 4, 16 or 64 force it
+ * (tests).  The result does not depend on it.
+ *
+ * Asynchronous on @hip_stream; no allocation, no host synchronisation.
+ * n == 0 is a no-op.  -EINVAL for a wrong in->size, a NULL ctx, in, out, src,
+ * src_off, len, dst or pkt_len, src_len or dst_len == UINT64_MAX, n > 2^40,
+ * a dst_stride < 16, not a multiple of 16 or > 2^20 when dst_off is NULL, a
+ * group other than 0, 4, 16 or 64, or an element array that is not aligned to
+ * its element; -EIO when the launch fails.
+ */
+enum {
+	GCL_COPY_COPIED = 0,
+	GCL_COPY_REFUSED,     /* the frame does not fit its destination */
+	GCL_COPY_BYTES,       /* frame bytes of the copied packets */
+	GCL_COPY_NR = 4,
+};
+struct gcl_copy_in {
+	uint32_t size;              /* sizeof(struct gcl_copy_in) */
+	uint32_t group;             /* 0: the library's choice; else lanes per packet: 4, 16 or 64 (tests) */
+	const uint8_t  *src;        /* device-visible: HBM, or a gcl_host_register'ed tx region */
+	uint64_t        src_len;    /* bytes at or past it read as 0, at any offset */
+	const uint64_t *src_off;    /* u64[n], any byte alignment */
+	const uint16_t *len;        /* u16[n]: txpkt cmd.len, tx.c:61-63 */
+	const uint8_t  *tx_olflags; /* optional u8[n]: txpkt cmd.olflags (OLFLAG_*, TXFLAG_*) */
+	const uint32_t *hash;       /* optional u32[n]: pkt->hash, tx.c:82 */
+	uint64_t        n;
+	uint32_t        len_hint;   /* typical frame length, only steers the library's choice of group; 0 = unknown */
+	uint32_t        dst_cap;    /* a frame longer than this is refused; 0 = no cap of its own */
+};
+struct gcl_copy_out {
+	uint8_t        *dst;        /* device: the rx pool (gcl_batch.frames of the batch to classify) */
+	uint64_t        dst_len;
+	const uint64_t *dst_off;    /* optional u64[n], any alignment; else i * dst_stride */
+	uint64_t        dst_stride; /* dst_off == NULL: multiple of 16, 16..2^20, as gcl_batch.stride */
+	uint16_t       *pkt_len;    /* u16[n]: len[i] when copied, 0 when refused */
+	uint8_t        *olflags;    /* optional u8[n]: gcl_loopback_olflags(tx_olflags ? tx_olflags[i] : 0) */
+	uint32_t       *rss;        /* optional u32[n]: hash ? hash[i] : 0 */
+};
+int gcl_copy_batch(struct gcl_ctx *ctx, const struct gcl_copy_in *in,
+                   const struct gcl_copy_out *out, uint64_t *counts, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
