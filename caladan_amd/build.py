@@ -2,7 +2,8 @@
 
 hipcc compiles the HIP kernels + C ABI (csrc/gcl_*.hip: the context, the
 batch kernels, the persistent rx loop, the transports and allocation, the
-generator); gcc compiles the host-side C (csrc/gcl_host.c, csrc/gcl_pcap.c);
+generator); gcc compiles the host-side C (csrc/gcl_host.c, csrc/gcl_pcap.c,
+csrc/gcl_sock.c);
 hipcc links them into caladan_amd/libgclassify.so.  The multi-GPU group (csrc/gcl_group.hip,
 include/gcl_group.h) is its own library, caladan_amd/libgclgroup.so, linked
 against libgclassify.so and RCCL, so that a single-GPU dataplane does not
@@ -24,10 +25,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("GCL_OFFLOAD_ARCH", "gfx950")
 
 SOURCES_HIP = ["gcl_ctx.hip", "gcl_batch.hip", "gcl_loop.hip", "gcl_xfer.hip", "gcl_gen.hip",
-               "gcl_plan.hip", "gcl_pack.hip", "gcl_csum.hip", "gcl_copy.hip"]
-SOURCES_C = ["gcl_host.c", "gcl_pcap.c"]
-DEPS = ["gcl_device.h", "gcl_kern.h", "gcl_ctx.h", "../../include/gclassify.h", "../../include/gcl_host.h",
-        "../../include/gcl_pcap.h"]
+               "gcl_plan.hip", "gcl_pack.hip", "gcl_csum.hip", "gcl_copy.hip", "gcl_sock.hip"]
+SOURCES_C = ["gcl_host.c", "gcl_pcap.c", "gcl_sock.c"]
+DEPS = ["gcl_device.h", "gcl_kern.h", "gcl_ctx.h", "gcl_sock.h", "../../include/gclassify.h",
+        "../../include/gcl_host.h", "../../include/gcl_pcap.h"]
 SOURCE_GROUP = "gcl_group.hip"
 DEPS_GROUP = ["../../include/gclassify.h", "../../include/gcl_group.h"]
 
@@ -176,6 +177,25 @@ def build_sanitized_copy(out_dir=None):
     return exe
 
 
+def build_sanitized_sock(out_dir=None):
+    """The ASan + UBSan host build of csrc/gcl_sock.c (the socket table, its
+    placement and the lookup of a batch on the CPU, with the probe of
+    csrc/gcl_sock.h that the GPU kernel shares) and of csrc/gcl_host.c (the
+    verdict widening the driver checks against), linked into
+    tests/fuzz/sock_fuzz.c: a stand-alone driver over random entry sets,
+    exactly sized heap frames and random verdict bytes.  Returns the driver's
+    path."""
+    out_dir = out_dir or os.path.join(ROOT, "build", "sanitize")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "sock_fuzz")
+    srcs = [os.path.join(ROOT, "tests", "fuzz", "sock_fuzz.c"), os.path.join(CSRC, "gcl_sock.c"),
+            os.path.join(CSRC, "gcl_host.c")]
+    if _stale(exe, srcs + [os.path.join(CSRC, d) for d in DEPS]):
+        _run(["gcc", "-std=gnu11", "-Wall", "-Wno-unused-parameter", *SANITIZE_FLAGS,
+              "-o", exe, *srcs, "-lm"])
+    return exe
+
+
 if __name__ == "__main__":
     if "--sanitize" in sys.argv:
         print(build_sanitized())
@@ -183,5 +203,6 @@ if __name__ == "__main__":
         print(build_sanitized_pack())
         print(build_sanitized_csum())
         print(build_sanitized_copy())
+        print(build_sanitized_sock())
     else:
         build(force="--force" in sys.argv, verbose_resources="--resources" in sys.argv)

@@ -61,6 +61,21 @@ struct gcl_ctx {
 		uint8_t *verd[4];        /* verdicts of one chunk (sized for 8-B verdicts) */
 		uint64_t *acc;           /* device counts | stats */
 	} e2e;
+	/* the socket table (gcl_sock.hip): the host object, created by the first
+	 * gcl_sock_set or gcl_sock_lookup, and its device copy.  The object's own
+	 * dirty flag says the copy is stale; the classify tables' is not involved. */
+	struct gcl_sock_tbl *sock;
+	struct SockDev {
+		uint8_t *dimg;       /* one device image */
+		uint8_t *staging;    /* pinned, as large */
+		size_t cap;
+		uint8_t hdr[16];     /* header of the image on the device */
+		hipEvent_t copied;   /* after the last upload: staging free, image ready */
+		hipStream_t up_stream;
+		int nusers;          /* streams that looked up since the last upload */
+		hipStream_t users[gclk::kImgUsers];
+		bool many;           /* more of them than users[] holds */
+	} sockdev;
 	int cur;
 	hipStream_t last_stream;
 	/* profiling */
@@ -89,6 +104,10 @@ int upload_tables(gcl_ctx *c, hipStream_t s);
 int wait_tables(gcl_ctx *c, hipStream_t s);
 /* a tune field, or @dflt where it is GCL_TUNE_AUTO */
 inline int32_t tuned(int32_t v, int32_t dflt) { return v == GCL_TUNE_AUTO ? dflt : v; }
+
+/* gcl_sock.hip */
+void sock_runtime_del(gcl_ctx *c, uint16_t uniqid); /* gcl_runtime_del: drop its entries */
+void sock_close(gcl_ctx *c);                        /* gcl_close: free the table and its copy */
 
 /* gcl_xfer.hip: device address of pinned / registered host memory, or NULL */
 void *mapped(const void *h);

@@ -70,6 +70,8 @@ extern "C" int gcl_open(int hip_device, const struct gcl_cfg *cfg, struct gcl_ct
 	c->dirty = true;
 	c->loop_dirty = true;
 	c->cur = 0;
+	c->sock = nullptr;
+	memset(&c->sockdev, 0, sizeof(c->sockdev));
 	c->last_stream = nullptr;
 	c->prof_ms = 0;
 	c->prof_launches = 0;
@@ -115,6 +117,7 @@ extern "C" void gcl_close(struct gcl_ctx *c)
 	if (c->loop)
 		gcl_rxloop_stop(c->loop);
 	(void)hipDeviceSynchronize();
+	sock_close(c);
 	for (int i = 0; i < 2; i++) {
 		(void)hipFree(c->dimg[i]);
 		for (int j = 0; j < kImgUsers; j++)
@@ -199,6 +202,7 @@ extern "C" int gcl_runtime_del(struct gcl_ctx *c, uint16_t uniqid)
 	if (!c || uniqid >= c->cfg.max_runtimes || !c->rt[uniqid].present)
 		return -ENOENT;
 	c->rt[uniqid] = gcl_ctx::Rt();
+	sock_runtime_del(c, uniqid);
 	c->dirty = true;
 	c->loop_dirty = true;
 	return 0;

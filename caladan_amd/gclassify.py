@@ -54,6 +54,15 @@ CSUM_BLOCK_PKTS, CSUM_BLOCKS_PER_CU = 256, 7
 COPY_COPIED, COPY_REFUSED, COPY_BYTES, COPY_NR = 0, 1, 2, 4
 # its launch (csrc/gcl_copy.hip): lanes per block, and the grid's cap
 COPY_THREADS, COPY_BLOCKS_PER_CU = 256, 6
+# gcl_sock_lookup: entry kinds, the answers that are not cookies, the counter slots
+SOCK_MATCH_3TUPLE, SOCK_MATCH_5TUPLE, SOCK_MAX_ENTRIES = 3, 5, 1 << 20
+SOCK_NA, SOCK_MISS, SOCK_MULTI, SOCK_COOKIE_MAX = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFEF
+SOCK_HIT5, SOCK_HIT3, SOCK_HIT3_ANY, SOCK_N_MULTI, SOCK_N_MISS, SOCK_N_NA, SOCK_NR = 0, 1, 2, 3, 4, 5, 8
+# its launch (csrc/gcl_sock.hip): packets a block takes per pass, and the grid's cap
+SOCK_BLOCK_PKTS, SOCK_BLOCKS_PER_CU = 256, 4
+# struct gcl_sock_entry as a numpy record
+SOCK_ENTRY_DTYPE = np.dtype([("lip", "<u4"), ("rip", "<u4"), ("lport", "<u2"), ("rport", "<u2"),
+                             ("proto", "u1"), ("match", "u1"), ("pad", "<u2"), ("cookie", "<u4")])
 STAT_NAMES = ["RX_UNREGISTERED_MAC", "RX_UNICAST_FAIL", "RX_BROADCAST_FAIL",
               "RX_FLOW_TAG_MATCH", "RX_UNHANDLED", "RX_HASH_MISSING", "RX_PULLED"]
 
@@ -102,6 +111,12 @@ class GclGenParams(ctypes.Structure):
 class GclOut(ctypes.Structure):
     _fields_ = [("verdicts", ctypes.c_void_p), ("runtime_counts", ctypes.c_void_p),
                 ("stats", ctypes.c_void_p), ("trans", ctypes.c_void_p)]
+
+
+class GclSockEntry(ctypes.Structure):
+    _fields_ = [("lip", ctypes.c_uint32), ("rip", ctypes.c_uint32), ("lport", ctypes.c_uint16),
+                ("rport", ctypes.c_uint16), ("proto", ctypes.c_uint8), ("match", ctypes.c_uint8),
+                ("pad", ctypes.c_uint16), ("cookie", ctypes.c_uint32)]
 
 
 class GclTrans(ctypes.Structure):
@@ -306,6 +321,15 @@ def _load():
         "gcl_plan_pack": (i32, [vp, ctypes.POINTER(GclPackIn), ctypes.POINTER(GclPackOut), vp]),
         "gcl_rx_csum": (i32, [vp, ctypes.POINTER(GclBatch), vp, vp, vp]),
         "gcl_rx_csum_flags": (ctypes.c_uint8, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint8]),
+        "gcl_sock_set": (i32, [vp, ctypes.c_uint16, vp, u32]),
+        "gcl_sock_lookup": (i32, [vp, ctypes.POINTER(GclBatch), vp, vp, vp, vp]),
+        "gcl_sock_tbl_new": (vp, []),
+        "gcl_sock_tbl_free": (None, [vp]),
+        "gcl_sock_tbl_set": (i32, [vp, ctypes.c_uint16, vp, u32]),
+        "gcl_sock_tbl_del": (i32, [vp, ctypes.c_uint16]),
+        "gcl_sock_tbl_hash_bits": (i32, [vp, u32]),
+        "gcl_sock_tbl_lookup_host": (i32, [vp, ctypes.c_uint8, ctypes.c_uint8, u32,
+                                           ctypes.POINTER(GclBatch), vp, vp, vp]),
         "gcl_copy_batch": (i32, [vp, ctypes.POINTER(GclCopyIn), ctypes.POINTER(GclCopyOut), vp, vp]),
         "gcl_copy_batch_host": (i32, [ctypes.POINTER(GclCopyIn), ctypes.POINTER(GclCopyOut), vp]),
         "gcl_host_deliver_packed": (u64, [vp, u32, vp, i32, vp, vp, vp, vp, u64, u64, vp,
@@ -445,6 +469,77 @@ def copy_batch_host(src, src_off, length, dst, dst_off=None, dst_stride=0, tx_ol
     _check(lib.gcl_copy_batch_host(ctypes.byref(cin), ctypes.byref(cout), _ptr(counts)),
            "gcl_copy_batch_host")
     return pkt_len, olflags, rss
+
+
+def sock_entries(entries):
+    """struct gcl_sock_entry[n] as a numpy record array (SOCK_ENTRY_DTYPE):
+    @entries is such an array already, or a sequence of GclSockEntry, of dicts
+    or of (lip, lport, proto, match, cookie[, rip, rport]) tuples."""
+    if isinstance(entries, np.ndarray):
+        if entries.dtype != SOCK_ENTRY_DTYPE:
+            raise ValueError("entries: not SOCK_ENTRY_DTYPE")
+        return np.ascontiguousarray(entries)
+    out = np.zeros(len(entries), dtype=SOCK_ENTRY_DTYPE)
+    for i, e in enumerate(entries):
+        if isinstance(e, GclSockEntry):
+            e = {f: getattr(e, f) for f, _ in GclSockEntry._fields_}
+        elif not isinstance(e, dict):
+            e = dict(zip(("lip", "lport", "proto", "match", "cookie", "rip", "rport"), e))
+        for f, v in e.items():
+            out[f][i] = v
+    return out
+
+
+class SockTable:
+    """The host-only socket table (gcl_sock_tbl_*, include/gcl_host.h): the
+    table of Classifier.sock_set / sock_lookup without a GPU."""
+
+    def __init__(self, hash_bits=None):
+        self._tbl = ctypes.c_void_p(lib.gcl_sock_tbl_new())
+        if not self._tbl:
+            raise MemoryError("gcl_sock_tbl_new")
+        if hash_bits is not None:
+            self.hash_bits(hash_bits)
+
+    def close(self):
+        if self._tbl:
+            lib.gcl_sock_tbl_free(self._tbl)
+            self._tbl = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def hash_bits(self, bits):
+        """The test knob: only the low @bits of the internal hash, from the next set on."""
+        return _check(lib.gcl_sock_tbl_hash_bits(self._tbl, bits), "gcl_sock_tbl_hash_bits")
+
+    def set(self, uniqid, entries):
+        e = sock_entries(entries)
+        return _check(lib.gcl_sock_tbl_set(self._tbl, uniqid, e.ctypes.data if len(e) else None, len(e)),
+                      "gcl_sock_tbl_set")
+
+    def delete(self, uniqid):
+        return _check(lib.gcl_sock_tbl_del(self._tbl, uniqid), "gcl_sock_tbl_del")
+
+    def lookup(self, frames, n, verdicts, vbytes, thread_bits=0, max_runtimes=GCL_MAX_PROC, stride=0,
+               offs=None, frames_len=None, sock=None, counts=None):
+        """gcl_sock_tbl_lookup_host over numpy arrays; returns (sock u32[n],
+        counts u64[SOCK_NR]), @counts accumulated when given."""
+        if _nbytes(verdicts) < vbytes * n or (offs is not None and _nbytes(offs) < 8 * n):
+            raise ValueError("per-packet array too small")
+        sock = np.empty(max(n, 1), dtype=np.uint32) if sock is None else sock
+        counts = np.zeros(SOCK_NR, dtype=np.uint64) if counts is None else counts
+        if _nbytes(sock) < 4 * n or _nbytes(counts) < 8 * SOCK_NR:
+            raise ValueError("output buffer too small")
+        b = GclBatch(frames=_ptr(frames), frames_len=_frames_len(frames, frames_len), stride=stride,
+                     offs=_ptr(offs), n=n)
+        _check(lib.gcl_sock_tbl_lookup_host(self._tbl, vbytes, thread_bits, max_runtimes, ctypes.byref(b),
+                                            _ptr(verdicts), _ptr(sock), _ptr(counts)),
+               "gcl_sock_tbl_lookup_host")
+        return sock[:n], counts
 
 
 def runtime_ip(r: int) -> int:
@@ -830,6 +925,38 @@ class Classifier:
         _check(lib.gcl_rx_csum(self._ctx, ctypes.byref(b), _ptr(olflags_out), _ptr(counts), stream),
                "gcl_rx_csum")
         return olflags_out
+
+    def sock_set(self, uniqid, entries):
+        """gcl_sock_set: replace runtime @uniqid's socket entries (sock_entries
+        says what @entries may be; an empty sequence clears them)."""
+        e = sock_entries(entries)
+        return _check(lib.gcl_sock_set(self._ctx, uniqid, e.ctypes.data if len(e) else None, len(e)),
+                      "gcl_sock_set")
+
+    def sock_lookup(self, frames, n, stride=0, verdicts=None, sock=None, counts=None, offs=None,
+                    frames_len=None, stream=None):
+        """gcl_sock_lookup: the socket demux of a classified batch on the GPU
+        (asynchronous).  @verdicts is the device array classify wrote, in the
+        context's width; @sock (int32, u32[n]) is allocated when not given;
+        @counts is a device u64[SOCK_NR], accumulated.  Returns @sock."""
+        if verdicts is None or _nbytes(verdicts) < self.vbytes * n:
+            raise ValueError("verdict buffer too small")
+        if offs is not None and _nbytes(offs) < 8 * n:
+            raise ValueError("per-packet array too small")
+        if counts is not None and _nbytes(counts) < 8 * SOCK_NR:
+            raise ValueError("counts buffer too small")
+        if sock is None:
+            import torch
+            dev = frames.device if hasattr(frames, "device") else None
+            sock = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        if _nbytes(sock) < 4 * n:
+            raise ValueError("sock buffer too small")
+        b = GclBatch(frames=_ptr(frames), frames_len=_frames_len(frames, frames_len),
+                     stride=stride, offs=_ptr(offs), olflags=None, rss=None,
+                     fdir_hi=None, pkt_len=None, n=n, dst_hint=None)
+        _check(lib.gcl_sock_lookup(self._ctx, ctypes.byref(b), _ptr(verdicts), _ptr(sock), _ptr(counts),
+                                   stream), "gcl_sock_lookup")
+        return sock
 
     def copy_batch(self, src, src_off, length, n, dst, dst_off=None, dst_stride=0, tx_olflags=None,
                    hash=None, src_len=None, dst_len=None, dst_cap=0, len_hint=0, group=0,

@@ -110,6 +110,42 @@ int gcl_copy_batch_host(const struct gcl_copy_in *in, const struct gcl_copy_out 
                         uint64_t *counts);
 
 /*
+ * The socket table of gcl_sock_set / gcl_sock_lookup (gclassify.h) as a
+ * host-only object: the same entry checks, the same table image and the same
+ * probe (one shared inline function), with no GPU.  A context embeds one.
+ *
+ * gcl_sock_tbl_new    - an empty table, or NULL (no memory).
+ * gcl_sock_tbl_set    - gcl_sock_set without -ENOENT: any @uniqid <
+ *                       GCL_MAX_PROC may hold entries (-EINVAL past it).
+ * gcl_sock_tbl_del    - drop @uniqid's entries; 0, or -EINVAL.
+ * gcl_sock_tbl_hash_bits - a test knob: use only the low @bits (1..32) of the
+ *                       table's internal hash from the next gcl_sock_tbl_set
+ *                       on, so that every key falls into a few home buckets:
+ *                       the longest kick chains, and the placement failure
+ *                       (-ENOSPC from gcl_sock_tbl_set, the previous set
+ *                       kept).  32 is the production value.  0 or -EINVAL.
+ * gcl_sock_tbl_lookup_host - the rule of gcl_sock_lookup over host pointers:
+ *                       @b, @verdicts (@vbytes wide: 8, 4, 2 or 1), @sock
+ *                       (u32[n]) and @counts (u64[GCL_SOCK_NR], ACCUMULATED,
+ *                       may be NULL) as there, @thread_bits and
+ *                       @max_runtimes what the context would have.  Any byte
+ *                       alignment of verdicts and sock is accepted.  0, or
+ *                       -EINVAL for a NULL tbl, b, verdicts or sock, a bad
+ *                       @vbytes, @thread_bits > 8, and the batches
+ *                       gcl_rx_csum refuses.  n == 0 is a no-op.
+ */
+struct gcl_sock_tbl;
+struct gcl_sock_tbl *gcl_sock_tbl_new(void);
+void gcl_sock_tbl_free(struct gcl_sock_tbl *tbl);
+int gcl_sock_tbl_set(struct gcl_sock_tbl *tbl, uint16_t uniqid, const struct gcl_sock_entry *e,
+                     uint32_t n);
+int gcl_sock_tbl_del(struct gcl_sock_tbl *tbl, uint16_t uniqid);
+int gcl_sock_tbl_hash_bits(struct gcl_sock_tbl *tbl, uint32_t bits);
+int gcl_sock_tbl_lookup_host(const struct gcl_sock_tbl *tbl, uint8_t vbytes, uint8_t thread_bits,
+                             uint32_t max_runtimes, const struct gcl_batch *b, const void *verdicts,
+                             uint32_t *sock, uint64_t *counts);
+
+/*
  * gcl_host_deliver - consume @n verdicts in order.
  * @clients_by_id  dp.clients_by_id (iokernel/defs.h:386), @max_runtimes long
  * @clients        dp.clients[0..nr_clients) (broadcast order, rx.c:175)

@@ -1019,6 +1019,109 @@ struct gcl_copy_out {
 int gcl_copy_batch(struct gcl_ctx *ctx, const struct gcl_copy_in *in,
                    const struct gcl_copy_out *out, uint64_t *counts, void *hip_stream);
 
+/*
+ * Socket demux: trans_lookup (runtime/net/transport.c:341-397), the step that
+ * ends the receive path.  Every TCP or UDP frame net_rx_one hands to
+ * net_rx_trans is matched against the receiving runtime's 5-tuple entries
+ * (its connections), then its 3-tuple entries (its listeners), then its
+ * listeners bound to address 0.  The classify kernel's GCL_CFG_TRANS_HASH
+ * gives a runtime the two bucket hashes; the runtime still walks its hash
+ * chains for every packet on its own cores, and the 2- and 1-byte verdict
+ * contexts have no hashes at all.  gcl_sock_lookup makes the whole lookup for
+ * a classified batch on the GPU, on every context: sock[i] is the cookie (the
+ * runtime's own name) of the entry trans_lookup would return for packet i.
+ *
+ * The table.  A context holds a set of entries per runtime, exact-match on
+ * (uniqid, match, proto, laddr[, raddr]), hashed by a hash of the library's
+ * own: the result depends on the keys only, never on trans_seed.
+ *
+ * gcl_sock_set - replace the whole entry set of runtime @uniqid (@n == 0
+ *   clears it); on any error the previous set stays in place.  Works on every
+ *   context, whatever its verdict width, and needs no GCL_CFG_TRANS_HASH.
+ *   -ENOENT: the runtime is not present.  -EINVAL: a NULL ctx, a NULL @e with
+ *   @n > 0, lport == 0 (port zero is reserved, transport.c:185), a match
+ *   other than GCL_SOCK_MATCH_*, a proto other than 6 or 17, or a cookie
+ *   above GCL_SOCK_COOKIE_MAX.  -EADDRINUSE: two 5-tuple entries with the
+ *   same key (the conflict check of __trans_table_add, transport.c:202-214).
+ *   -ENOSPC: the context would hold more than GCL_SOCK_MAX_ENTRIES, or the
+ *   table could not place every key (not seen at its load of <= 1/2).
+ *   -ENOMEM.  Several 3-tuple entries with the same key are allowed: they are
+ *   the reference's reuse_port listeners, among which trans_lookup picks by
+ *   this_thread_id() (transport.c:392-396); a lookup that matches them
+ *   answers GCL_SOCK_MULTI and the runtime makes that choice itself.
+ *   rip, rport and pad of a 3-tuple entry are ignored.
+ *   gcl_runtime_del drops the runtime's entries.  Changes are applied on the
+ *   stream of the next gcl_sock_lookup, before its kernel (the snapshot
+ *   semantics of the runtime tables); the classify tables and their upload
+ *   are not touched.
+ *
+ * gcl_sock_lookup - asynchronous on @hip_stream.  Frames are addressed
+ *   exactly as gcl_rx_csum addresses them (frames, frames_len, stride or offs
+ *   at any byte alignment; a byte at or past frames_len reads 0, an offset at
+ *   or past frames_len is a frame of zeros); the side arrays of @b are
+ *   ignored.  @verdicts is a device array in the context's own width (8, 4, 2
+ *   or 1 B) as gcl_classify wrote it, aligned to its element; @sock a device
+ *   u32[n], 4-B aligned; @counts a device u64[GCL_SOCK_NR], ACCUMULATED, may
+ *   be NULL; per call the six counters sum to n.
+ *
+ *   Packet i.  u is the verdict's runtime for a DELIVER or WAKE verdict:
+ *   uniqid (8- and 4-byte verdicts), or q >> thread_bits of the 2- and 1-byte
+ *   forms (gcl_verdict2_to4 / gcl_verdict1_to4, gcl_host.h).
+ *     GCL_SOCK_NA (N_NA) when the verdict is any other action (the undefined
+ *       2-B kind 0x8000 included), when u >= max_runtimes, or when the frame
+ *       fails the predicate that sets GCL_ACT_F_TRANS (struct gcl_trans):
+ *       bytes 12-13 0x0800, version 4, IHL 5, the MF test of ip_hdr_supported
+ *       as written, protocol 6 or 17.
+ *     Otherwise, as transport.c:361-391, with proto = byte 23, laddr = (bytes
+ *       30-33, bytes 36-37) and raddr = (bytes 26-29, bytes 34-35) in host
+ *       order, the first of:
+ *         the cookie of u's 5-tuple entry (proto, laddr, raddr)      HIT5
+ *         the cookie of u's 3-tuple entry (proto, laddr)             HIT3
+ *         the cookie of u's 3-tuple entry (proto, (0, laddr.port))   HIT3_ANY
+ *         GCL_SOCK_MISS (trans_lookup returns NULL)                  N_MISS
+ *       A 3-tuple step that finds several listeners on its key answers
+ *       GCL_SOCK_MULTI, counted N_MULTI and not as a hit, and ends the
+ *       search as transport.c:384-396 does.
+ *
+ *   Guarantee: no content of frames, offs, verdicts or the entries causes a
+ *   read outside frames[0, frames_len), the n-element arrays or the table
+ *   image, or a write outside sock[0, n).  A lookup reads a fixed number of
+ *   table words (twelve 16-B keys and one cookie).
+ *
+ *   No allocation and no host synchronisation beyond the table upload after
+ *   a change.  n == 0 is a no-op.  -EINVAL for a NULL ctx, b, verdicts or
+ *   sock, a misaligned verdicts or sock, and the batches gcl_rx_csum refuses;
+ *   -ENOMEM or -EIO when the table upload fails, -EIO when the launch fails.
+ */
+#define GCL_SOCK_MATCH_3TUPLE 3   /* listener: (proto, laddr)            */
+#define GCL_SOCK_MATCH_5TUPLE 5   /* connection: (proto, laddr, raddr)   */
+#define GCL_SOCK_MAX_ENTRIES (1u << 20)   /* per context, all runtimes   */
+#define GCL_SOCK_NA    0xFFFFFFFFu  /* not a packet net_rx_trans sees     */
+#define GCL_SOCK_MISS  0xFFFFFFFEu  /* trans_lookup returns NULL          */
+#define GCL_SOCK_MULTI 0xFFFFFFFDu  /* >= 2 listeners share the 3-tuple   */
+#define GCL_SOCK_COOKIE_MAX 0xFFFFFFEFu
+struct gcl_sock_entry {            /* host order, as struct netaddr      */
+	uint32_t lip, rip;             /* rip/rport ignored for 3TUPLE       */
+	uint16_t lport, rport;
+	uint8_t  proto;                /* 6 or 17                            */
+	uint8_t  match;                /* GCL_SOCK_MATCH_*                   */
+	uint16_t pad;
+	uint32_t cookie;               /* the runtime's own name for the entry */
+};
+int gcl_sock_set(struct gcl_ctx *ctx, uint16_t uniqid, const struct gcl_sock_entry *e, uint32_t n);
+
+enum {
+	GCL_SOCK_HIT5 = 0,    /* a connection */
+	GCL_SOCK_HIT3,        /* a listener on the packet's own address */
+	GCL_SOCK_HIT3_ANY,    /* a listener on address 0 */
+	GCL_SOCK_N_MULTI,
+	GCL_SOCK_N_MISS,
+	GCL_SOCK_N_NA,
+	GCL_SOCK_NR = 8,      /* padded */
+};
+int gcl_sock_lookup(struct gcl_ctx *ctx, const struct gcl_batch *b, const void *verdicts,
+                    uint32_t *sock, uint64_t *counts, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
