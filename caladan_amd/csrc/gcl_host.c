@@ -272,6 +272,105 @@ int gcl_copy_batch_host(const struct gcl_copy_in *in, const struct gcl_copy_out 
 	return 0;
 }
 
+/* __raw_cksum (inc/net/chksum.h) folded: @len bytes as 16-bit words in memory
+ * order, an odd last byte the low byte of a last word, plus @sum */
+static uint32_t l4_fold(const uint8_t *p, size_t len, uint64_t sum)
+{
+	size_t i;
+
+	for (i = 0; i + 1 < len; i += 2)
+		sum += p[i] | (uint32_t)p[i + 1] << 8;
+	if (i < len)
+		sum += p[i];
+	while (sum >> 16)
+		sum = (sum & 0xFFFF) + (sum >> 16);
+	return (uint32_t)sum;
+}
+
+/* The rule of gcl_l4_csum (gclassify.h) on the CPU: ipv4_cksum and
+ * ipv4_udptcp_cksum (inc/net/chksum.h) as the runtime fills them, and the
+ * check of the same sum on receive. */
+int gcl_l4_csum_host(const struct gcl_batch *b, const struct gcl_l4_in *in, uint8_t *status,
+                     uint64_t *counts)
+{
+	uint64_t c[GCL_L4C_NR] = {0};
+
+	if (!b || !in || !status || in->size != sizeof(*in) || in->mode > GCL_L4_FILL ||
+	    (in->group != 0 && in->group != 4 && in->group != 16 && in->group != 64))
+		return -EINVAL;
+	if (b->n == 0)
+		return 0;
+	if (!b->frames || b->frames_len == UINT64_MAX || b->n > (1ull << 40) ||
+	    (!b->offs && (b->stride < 16 || (b->stride & 15) || b->stride > (1u << 20))) ||
+	    !b->pkt_len || ((uintptr_t)b->pkt_len & 1))
+		return -EINVAL;
+	for (uint64_t i = 0; i < b->n; i++) {
+		const uint64_t raw = b->offs ? b->offs[i] : i * b->stride;
+		const uint64_t o = raw < b->frames_len ? raw : b->frames_len;
+		const uint64_t avail = b->frames_len - o;
+		const uint64_t L = b->pkt_len[i] < avail ? b->pkt_len[i] : avail;
+		uint8_t *f = (uint8_t *)b->frames + o; /* FILL writes: the caller owns the memory */
+		const uint8_t fl = in->mode != GCL_L4_FILL ? 0 : in->tx_olflags ? in->tx_olflags[i] : 3;
+		uint8_t st = GCL_L4_NA;
+		uint32_t tot = 0, l4len = 0;
+		bool ip_ok, l4_ok = false;
+
+		ip_ok = L >= 34 && f[12] == (GCL_ETHTYPE_IP >> 8) && f[13] == (GCL_ETHTYPE_IP & 0xFF) &&
+		        f[14] == 0x45;
+		if (ip_ok) {
+			const uint32_t frag = (uint32_t)f[20] << 8 | f[21]; /* host order: MF 0x2000, offset 0x1FFF */
+			const uint8_t proto = f[23];
+
+			tot = (uint32_t)f[16] << 8 | f[17];
+			l4_ok = !(frag & 0x3FFF) && (proto == 6 || proto == 17) &&
+			        tot >= 20u + (proto == 6 ? 20u : 8u) && 14ull + tot <= L;
+			l4len = tot - 20;
+		}
+		if (ip_ok && (fl & 1)) {
+			f[24] = f[25] = 0;
+			const uint32_t v = ~l4_fold(f + 14, 20, 0) & 0xFFFF;
+			f[24] = (uint8_t)v;
+			f[25] = (uint8_t)(v >> 8);
+			st |= GCL_L4_FILLED_IP;
+			c[GCL_L4C_FILLED_IP]++;
+		}
+		if (l4_ok) {
+			const uint8_t proto = f[23];
+			uint8_t *fld = f + (proto == 6 ? 50 : 40);
+			/* the pseudo-header's words in memory order: the addresses
+			 * as they lie in the frame, {0, proto}, hton16(l4len) */
+			const uint64_t ph = l4_fold(f + 26, 8, 0) + ((uint32_t)proto << 8) +
+			                    ((l4len >> 8) | (l4len & 0xFF) << 8);
+
+			if (in->mode == GCL_L4_FILL) {
+				if (fl & 2) {
+					fld[0] = fld[1] = 0;
+					uint32_t v = ~l4_fold(f + 34, l4len, ph) & 0xFFFF;
+					if (v == 0)
+						v = 0xFFFF;
+					fld[0] = (uint8_t)v;
+					fld[1] = (uint8_t)(v >> 8);
+					st |= GCL_L4_FILLED_L4;
+					c[GCL_L4C_FILLED_L4]++;
+					c[GCL_L4C_BYTES] += l4len;
+				}
+			} else if (proto == 17 && !fld[0] && !fld[1]) {
+				st = GCL_L4_NONE;
+			} else {
+				st = l4_fold(f + 34, l4len, ph) == 0xFFFF ? GCL_L4_GOOD : GCL_L4_BAD;
+				c[GCL_L4C_BYTES] += l4len;
+			}
+		}
+		status[i] = st;
+		c[(st & 0xF) == GCL_L4_GOOD ? GCL_L4C_GOOD : (st & 0xF) == GCL_L4_BAD ? GCL_L4C_BAD :
+		  (st & 0xF) == GCL_L4_NONE ? GCL_L4C_NONE : GCL_L4C_NA]++;
+	}
+	if (counts)
+		for (int k = 0; k < GCL_L4C_NR; k++)
+			counts[k] += c[k];
+	return 0;
+}
+
 /* rx_send_to_runtime (rx.c:50-73) for the flow_tbl slot @slot of runtime @p
  * (hash % thread_count: every DELIVER or WAKE verdict carries it), or, when
  * @slot < 0, the slot of @hash.  The flow_tbl and the active count are read

@@ -54,6 +54,13 @@ CSUM_BLOCK_PKTS, CSUM_BLOCKS_PER_CU = 256, 7
 COPY_COPIED, COPY_REFUSED, COPY_BYTES, COPY_NR = 0, 1, 2, 4
 # its launch (csrc/gcl_copy.hip): lanes per block, and the grid's cap
 COPY_THREADS, COPY_BLOCKS_PER_CU = 256, 6
+# gcl_l4_csum: modes, the status byte, the counter slots
+L4_VERIFY, L4_FILL = 0, 1
+L4_NA, L4_GOOD, L4_BAD, L4_NONE, L4_FILLED_IP, L4_FILLED_L4 = 0, 1, 2, 3, 0x10, 0x20
+(L4C_GOOD, L4C_BAD, L4C_NONE, L4C_NA, L4C_FILLED_IP, L4C_FILLED_L4, L4C_BYTES) = range(7)
+L4C_NR = 8
+# its launch (csrc/gcl_l4.hip): lanes per block, and the grid's cap
+L4_THREADS, L4_BLOCKS_PER_CU = 256, 7
 # gcl_sock_lookup: entry kinds, the answers that are not cookies, the counter slots
 SOCK_MATCH_3TUPLE, SOCK_MATCH_5TUPLE, SOCK_MAX_ENTRIES = 3, 5, 1 << 20
 SOCK_NA, SOCK_MISS, SOCK_MULTI, SOCK_COOKIE_MAX = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFEF
@@ -251,6 +258,11 @@ class GclCopyOut(ctypes.Structure):
                 ("olflags", ctypes.c_void_p), ("rss", ctypes.c_void_p)]
 
 
+class GclL4In(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("group", ctypes.c_uint32),
+                ("len_hint", ctypes.c_uint32), ("tx_olflags", ctypes.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} missing: run `python caladan_amd/build.py` "
@@ -321,6 +333,8 @@ def _load():
         "gcl_plan_pack": (i32, [vp, ctypes.POINTER(GclPackIn), ctypes.POINTER(GclPackOut), vp]),
         "gcl_rx_csum": (i32, [vp, ctypes.POINTER(GclBatch), vp, vp, vp]),
         "gcl_rx_csum_flags": (ctypes.c_uint8, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint8]),
+        "gcl_l4_csum": (i32, [vp, ctypes.POINTER(GclBatch), ctypes.POINTER(GclL4In), vp, vp, vp]),
+        "gcl_l4_csum_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclL4In), vp, vp]),
         "gcl_sock_set": (i32, [vp, ctypes.c_uint16, vp, u32]),
         "gcl_sock_lookup": (i32, [vp, ctypes.POINTER(GclBatch), vp, vp, vp, vp]),
         "gcl_sock_tbl_new": (vp, []),
@@ -469,6 +483,38 @@ def copy_batch_host(src, src_off, length, dst, dst_off=None, dst_stride=0, tx_ol
     _check(lib.gcl_copy_batch_host(ctypes.byref(cin), ctypes.byref(cout), _ptr(counts)),
            "gcl_copy_batch_host")
     return pkt_len, olflags, rss
+
+
+def _l4_structs(frames, n, stride, offs, pkt_len, frames_len, mode, tx_olflags, group, len_hint,
+                status, counts):
+    """The two structs of gcl_l4_csum / gcl_l4_csum_host, sizes checked."""
+    for arr, w in ((offs, 8), (pkt_len, 2), (tx_olflags, 1), (status, 1)):
+        if arr is not None and _nbytes(arr) < w * n:
+            raise ValueError("per-packet array too small")
+    if counts is not None and _nbytes(counts) < 8 * L4C_NR:
+        raise ValueError("counts buffer too small")
+    b = GclBatch(frames=_ptr(frames), frames_len=_frames_len(frames, frames_len), stride=stride,
+                 offs=_ptr(offs), olflags=None, rss=None, fdir_hi=None, pkt_len=_ptr(pkt_len), n=n,
+                 dst_hint=None)
+    lin = GclL4In(size=ctypes.sizeof(GclL4In), mode=mode, group=group, len_hint=len_hint,
+                  tx_olflags=_ptr(tx_olflags))
+    return b, lin
+
+
+def l4_csum_host(frames, pkt_len, mode=L4_VERIFY, stride=0, offs=None, n=None, frames_len=None,
+                 tx_olflags=None, status=None, counts=None):
+    """gcl_l4_csum_host: the rule of Classifier.l4_csum on the CPU over numpy
+    arrays (L4_FILL writes the checksum fields into @frames in place).
+    @status (uint8[n]) is allocated when None; @counts is a u64[L4C_NR],
+    accumulated.  Returns @status."""
+    n = len(pkt_len) if n is None else n
+    if status is None:
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+    b, lin = _l4_structs(frames, n, stride, offs, pkt_len, frames_len, mode, tx_olflags, 0, 0, status,
+                         counts)
+    _check(lib.gcl_l4_csum_host(ctypes.byref(b), ctypes.byref(lin), _ptr(status), _ptr(counts)),
+           "gcl_l4_csum_host")
+    return status
 
 
 def sock_entries(entries):
@@ -925,6 +971,27 @@ class Classifier:
         _check(lib.gcl_rx_csum(self._ctx, ctypes.byref(b), _ptr(olflags_out), _ptr(counts), stream),
                "gcl_rx_csum")
         return olflags_out
+
+    def l4_csum(self, frames, n, pkt_len, mode=L4_VERIFY, stride=0, offs=None, frames_len=None,
+                tx_olflags=None, status=None, counts=None, len_hint=0, group=0, stream=None):
+        """gcl_l4_csum: the TCP/UDP checksum of every eligible packet of the
+        batch checked (L4_VERIFY) or, with the IPv4 header checksum, written
+        into @frames (L4_FILL) on the GPU (asynchronous).  @pkt_len (int16,
+        u16[n]) is required; @tx_olflags (uint8) says per packet which fields
+        FILL writes (None: both); @status (uint8) is allocated on @frames'
+        device when None; @counts is a device u64[L4C_NR], accumulated.
+        Returns @status."""
+        if pkt_len is None:
+            raise ValueError("pkt_len is required")
+        if status is None:
+            import torch
+            dev = frames.device if hasattr(frames, "device") else None
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        b, lin = _l4_structs(frames, n, stride, offs, pkt_len, frames_len, mode, tx_olflags, group,
+                             len_hint, status, counts)
+        _check(lib.gcl_l4_csum(self._ctx, ctypes.byref(b), ctypes.byref(lin), _ptr(status),
+                               _ptr(counts), stream), "gcl_l4_csum")
+        return status
 
     def sock_set(self, uniqid, entries):
         """gcl_sock_set: replace runtime @uniqid's socket entries (sock_entries

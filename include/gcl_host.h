@@ -110,6 +110,21 @@ int gcl_copy_batch_host(const struct gcl_copy_in *in, const struct gcl_copy_out 
                         uint64_t *counts);
 
 /*
+ * gcl_l4_csum_host - the rule of gcl_l4_csum (gclassify.h) on the CPU over
+ * host pointers, for the batches the GPU did not see: the runtime's own
+ * ipv4_cksum and ipv4_udptcp_cksum fill (runtime/net/core.c:612-617,
+ * runtime/net/tcp_out.c:33-39) in GCL_L4_FILL, the check of the same sum in
+ * GCL_L4_VERIFY.  @b and @in are gcl_l4_csum's structs with every pointer a
+ * host pointer (in->group is checked, in->len_hint not looked at); @status is
+ * u8[n]; @counts is a host u64[GCL_L4C_NR], ACCUMULATED, may be NULL.  The
+ * same status bytes and counts, the same bytes written by FILL and the same
+ * guarantee.  0, or -EINVAL for what gcl_l4_csum refuses (the ctx apart).
+ * n == 0 is a no-op.
+ */
+int gcl_l4_csum_host(const struct gcl_batch *b, const struct gcl_l4_in *in, uint8_t *status,
+                     uint64_t *counts);
+
+/*
  * The socket table of gcl_sock_set / gcl_sock_lookup (gclassify.h) as a
  * host-only object: the same entry checks, the same table image and the same
  * probe (one shared inline function), with no GPU.  A context embeds one.

@@ -926,6 +926,114 @@ int gcl_rx_csum(struct gcl_ctx *ctx, const struct gcl_batch *b, uint8_t *olflags
                 uint64_t *counts, void *hip_stream);
 
 /*
+ * TCP/UDP checksum offload, both directions: what the reference asks of the
+ * NIC with IPV4_CKSUM | UDP_CKSUM | TCP_CKSUM (iokernel/dpdk.c:80,
+ * iokernel/tx.c:67-70), for batches that have no NIC to do it.
+ *
+ * GCL_L4_FILL is the transmit side.  With cfg.tx_offloads_disabled
+ * (dpdk.c:140-148) every runtime runs ipv4_udptcp_cksum over the whole
+ * segment (runtime/net/tcp_out.c:33-39) and ipv4_cksum (runtime/net/core.c:
+ * 612-617) on its own cores; FILL writes those two fields for a batch of
+ * frames on the GPU.  GCL_L4_VERIFY is the receive side, which the reference
+ * leaves to the NIC entirely (nothing under runtime/net checks a TCP or UDP
+ * checksum): a pcap replay, a TAP or virtual function, or a looped-back frame
+ * (whose TCP field holds only the pseudo-header sum) reaches a socket with
+ * its payload unchecked unless somebody sums it.
+ *
+ * Packet i has o = its offset clamped to frames_len (b->offs[i], or
+ * i * b->stride), avail = frames_len - o and L = min(b->pkt_len[i], avail):
+ * the mbuf's bytes that exist.  No byte at or past o + L enters any result,
+ * and none is written.
+ *
+ *   IP-eligible: L >= 34, frame bytes 12-13 are 0x0800, version 4 and IHL 5
+ *     (ip_hdr_supported, and the fixed l3_len of tx.c:72).
+ *   L4-eligible: IP-eligible, not a fragment (MF clear and fragment offset 0,
+ *     on the host-order field), protocol 6 or 17, and tot = ntoh16(bytes
+ *     16-17) with tot >= 20 + (TCP ? 20 : 8) and 14 + tot <= L (the length
+ *     test of net_rx_one, core.c:283-285).  l4len = tot - 20; bytes past
+ *     14 + tot (Ethernet padding) are not summed, as after mbuf_trim.
+ *   S: the 16-bit end-around-carry fold of the L4 bytes [34, 34 + l4len) as
+ *     16-bit words in memory order (an odd last byte is the low byte of a
+ *     last word) plus the pseudo-header {saddr, daddr, 0, proto,
+ *     hton16(l4len)} of the frame's own addresses: __raw_cksum and
+ *     ipv4_phdr_cksum of inc/net/chksum.h.
+ *
+ * VERIFY writes status and counts only.  status[i] is GCL_L4_NA when the
+ * packet is not L4-eligible, GCL_L4_NONE for UDP whose checksum field is 0,
+ * GCL_L4_GOOD when S over the bytes as they stand is 0xFFFF, GCL_L4_BAD when
+ * it is not; per call GOOD + BAD + NONE + NA = n.
+ *
+ * FILL, with f = in->tx_olflags ? in->tx_olflags[i] : 3 (txpkt cmd.olflags):
+ *   bit 0 (OLFLAG_IP_CHKSUM) and IP-eligible: frame bytes 24-25 become
+ *     ipv4_cksum of the header with that field taken as 0; status gets
+ *     GCL_L4_FILLED_IP.
+ *   bit 1 (OLFLAG_TCP_CHKSUM) and L4-eligible: the L4 checksum field (bytes
+ *     50-51 for TCP, 40-41 for UDP) is taken as 0 whatever it held (the
+ *     runtime leaves the pseudo-header sum there for the NIC) and becomes
+ *     ipv4_udptcp_cksum's value, ~S & 0xFFFF with 0 replaced by 0xFFFF for
+ *     both protocols; status gets GCL_L4_FILLED_L4.
+ *   The status low nibble is GCL_L4_NA.  The two fills do not feed each
+ *   other: the IP field is outside the bytes S covers (the pseudo-header
+ *   takes only the addresses) and the L4 field is outside the IP header.
+ *   FILL writes through b->frames (the const is the struct's; the caller owns
+ *   the memory) and writes only the two or four checksum bytes of a filled
+ *   packet, each with a store of its own width or narrower: no wider word is
+ *   read-modify-written.  Frames that overlap are the caller's error in FILL
+ *   (the fields are then unspecified); nothing is written out of bounds even
+ *   so.
+ *
+ * Frames are addressed as gcl_rx_csum addresses them (frames, frames_len,
+ * stride or offs at any byte alignment); b->pkt_len (u16[n], 2-B aligned) is
+ * REQUIRED here; rss, fdir_hi, dst_hint and olflags are ignored.  Every
+ * pointer is a device pointer.  @status is u8[n].  @counts is a device
+ * u64[GCL_L4C_NR], ACCUMULATED, may be NULL: GOOD, BAD, NONE and NA count the
+ * status low nibbles (so FILL adds n to NA), FILLED_IP and FILLED_L4 the two
+ * bits, and BYTES adds l4len of every packet judged GOOD or BAD (VERIFY) or
+ * FILLED_L4 (FILL).  No content of frames,
+ * offs, pkt_len or tx_olflags causes a read outside frames[0, frames_len) or
+ * the n-element arrays, or a write outside status[0, n), counts and the
+ * checksum bytes above, which lie inside [o, o + L).
+ *
+ * in->group = 0 lets the library choose how many lanes sum one packet from
+ * in->len_hint (the typical frame length, 0 = unknown); 4, 16 or 64 force it
+ * (tests).  The result does not depend on it.
+ *
+ * Asynchronous on @hip_stream; no allocation, no host synchronisation.
+ * n == 0 is a no-op.  -EINVAL for a NULL ctx, b, in or status, a wrong
+ * in->size, a mode other than VERIFY or FILL, a group other than 0, 4, 16 or
+ * 64, a NULL pkt_len or one that is not 2-B aligned, and the batches
+ * gcl_rx_csum refuses; -EIO when the launch fails.
+ */
+enum gcl_l4_mode { GCL_L4_VERIFY = 0, GCL_L4_FILL = 1 };
+/* status byte, low nibble: the verdict of the L4 check */
+#define GCL_L4_NA    0   /* not a datagram this call judges */
+#define GCL_L4_GOOD  1
+#define GCL_L4_BAD   2
+#define GCL_L4_NONE  3   /* VERIFY: UDP with checksum field 0 (no checksum sent) */
+/* FILL: or-ed in */
+#define GCL_L4_FILLED_IP 0x10
+#define GCL_L4_FILLED_L4 0x20
+enum {
+	GCL_L4C_GOOD = 0,
+	GCL_L4C_BAD,
+	GCL_L4C_NONE,
+	GCL_L4C_NA,
+	GCL_L4C_FILLED_IP,
+	GCL_L4C_FILLED_L4,
+	GCL_L4C_BYTES,        /* L4 bytes of the packets whose S was used */
+	GCL_L4C_NR = 8,
+};
+struct gcl_l4_in {
+	uint32_t size;      /* sizeof(struct gcl_l4_in) */
+	uint32_t mode;      /* enum gcl_l4_mode */
+	uint32_t group;     /* 0: the library's choice; else lanes per packet: 4, 16 or 64 (tests) */
+	uint32_t len_hint;  /* typical frame length, only steers the choice of group; 0 = unknown */
+	const uint8_t *tx_olflags; /* FILL: optional u8[n] txpkt cmd.olflags; NULL = IP and L4 for every packet */
+};
+int gcl_l4_csum(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct gcl_l4_in *in,
+                uint8_t *status, uint64_t *counts, void *hip_stream);
+
+/*
  * The loopback frame copy: copy_batch(src_bufs, rx_bufs, n_bufs, rx_one_pkt)
  * of rx_loopback (iokernel/rx.c:264, iokernel/dma.c:167-191), the step between
  * the dst_ip lookups (gcl_batch.dst_hint) and rx_one_pkt (gcl_classify).  For
