@@ -25,9 +25,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("GCL_OFFLOAD_ARCH", "gfx950")
 
 SOURCES_HIP = ["gcl_ctx.hip", "gcl_batch.hip", "gcl_loop.hip", "gcl_xfer.hip", "gcl_gen.hip",
-               "gcl_plan.hip", "gcl_pack.hip", "gcl_csum.hip", "gcl_copy.hip", "gcl_sock.hip", "gcl_l4.hip"]
+               "gcl_plan.hip", "gcl_pack.hip", "gcl_csum.hip", "gcl_copy.hip", "gcl_sock.hip", "gcl_l4.hip",
+               "gcl_payload.hip"]
 SOURCES_C = ["gcl_host.c", "gcl_pcap.c", "gcl_sock.c"]
-DEPS = ["gcl_device.h", "gcl_kern.h", "gcl_ctx.h", "gcl_sock.h", "../../include/gclassify.h",
+DEPS = ["gcl_device.h", "gcl_kern.h", "gcl_ctx.h", "gcl_sock.h", "gcl_pay.h", "../../include/gclassify.h",
         "../../include/gcl_host.h", "../../include/gcl_pcap.h"]
 SOURCE_GROUP = "gcl_group.hip"
 DEPS_GROUP = ["../../include/gclassify.h", "../../include/gcl_group.h"]
@@ -211,6 +212,23 @@ def build_sanitized_l4(out_dir=None):
     return exe
 
 
+def build_sanitized_pay(out_dir=None):
+    """The same ASan + UBSan host build of csrc/gcl_host.c, linked into
+    tests/fuzz/pay_fuzz.c: a stand-alone driver of gcl_l4_payload_host (the
+    payload descriptors and the packed layout on the CPU, with the rule of
+    csrc/gcl_pay.h that the GPU kernel shares) over exactly sized heap arrays
+    with hostile offsets, lengths, orders and segment starts.  Returns the
+    driver's path."""
+    out_dir = out_dir or os.path.join(ROOT, "build", "sanitize")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "pay_fuzz")
+    srcs = [os.path.join(ROOT, "tests", "fuzz", "pay_fuzz.c"), os.path.join(CSRC, "gcl_host.c")]
+    if _stale(exe, srcs + [os.path.join(CSRC, d) for d in DEPS]):
+        _run(["gcc", "-std=gnu11", "-Wall", "-Wno-unused-parameter", *SANITIZE_FLAGS,
+              "-o", exe, *srcs, "-lm"])
+    return exe
+
+
 if __name__ == "__main__":
     if "--sanitize" in sys.argv:
         print(build_sanitized())
@@ -220,5 +238,6 @@ if __name__ == "__main__":
         print(build_sanitized_copy())
         print(build_sanitized_sock())
         print(build_sanitized_l4())
+        print(build_sanitized_pay())
     else:
         build(force="--force" in sys.argv, verbose_resources="--resources" in sys.argv)

@@ -8,6 +8,7 @@
 
 #include "../../include/gcl_host.h"
 #include "../../include/gclassify.h"
+#include "gcl_pay.h"
 
 #define ROT(x, k) (((x) << (k)) | ((x) >> (32 - (k))))
 
@@ -367,6 +368,70 @@ int gcl_l4_csum_host(const struct gcl_batch *b, const struct gcl_l4_in *in, uint
 	}
 	if (counts)
 		for (int k = 0; k < GCL_L4C_NR; k++)
+			counts[k] += c[k];
+	return 0;
+}
+
+/* The rule of gcl_l4_payload (gclassify.h) on the CPU: gcl_pay_rule of
+ * gcl_pay.h for every list entry in turn, the layout a running sum. */
+int gcl_l4_payload_host(const struct gcl_batch *b, const struct gcl_pay_in *in,
+                        const struct gcl_pay_out *out, uint64_t *counts)
+{
+	uint64_t c[GCL_PAYC_NR] = {0}, at = 0;
+
+	if (!b || !in || !out || in->size != sizeof(*in) || !gcl_pay_align_ok(in->align) ||
+	    (!in->order && in->m != b->n) || in->m > (1ull << 31) || in->blocks > GCL_PAY_MAX_BLOCKS)
+		return -EINVAL;
+	if (!out->src_off || !out->len || !out->dst_off || !out->kind || !out->total ||
+	    !in->seg_off != !out->seg_bytes)
+		return -EINVAL;
+	if (((uintptr_t)out->src_off & 7) || ((uintptr_t)out->len & 1) || ((uintptr_t)out->dst_off & 7) ||
+	    ((uintptr_t)out->meta & 15) || ((uintptr_t)out->seg_bytes & 7) || ((uintptr_t)out->total & 7) ||
+	    ((uintptr_t)in->order & 3) || ((uintptr_t)in->sock & 3) || ((uintptr_t)in->seg_off & 3) ||
+	    ((uintptr_t)counts & 7))
+		return -EINVAL;
+	if (in->m && (!b->frames || b->frames_len == UINT64_MAX || b->n > (1ull << 40) ||
+	              (!b->offs && (b->stride < 16 || (b->stride & 15) || b->stride > (1u << 20))) ||
+	              !b->pkt_len || ((uintptr_t)b->pkt_len & 1)))
+		return -EINVAL;
+	const uint32_t amask = in->align ? in->align - 1 : 0;
+
+	for (uint64_t j = 0; j < in->m; j++) {
+		const uint64_t i = in->order ? in->order[j] : j;
+		struct gcl_pay_desc r = {0, 0, GCL_PAY_OOR, {0, 0, 0, 0}};
+
+		if (i < b->n) {
+			const uint64_t raw = b->offs ? b->offs[i] : i * b->stride;
+			const uint64_t o = raw < b->frames_len ? raw : b->frames_len;
+			const uint64_t avail = b->frames_len - o;
+			const uint64_t L = b->pkt_len[i] < avail ? b->pkt_len[i] : avail;
+			uint8_t h[48] = {0};
+			uint32_t d[9];
+
+			if (avail)
+				memcpy(h, b->frames + o, avail < sizeof(h) ? avail : sizeof(h));
+			for (int x = 0; x < 9; x++)
+				d[x] = h[12 + 4 * x] | (uint32_t)h[13 + 4 * x] << 8 | (uint32_t)h[14 + 4 * x] << 16 |
+				       (uint32_t)h[15 + 4 * x] << 24;
+			r = gcl_pay_rule(d, o, L, in->l4_status != NULL, in->l4_status ? in->l4_status[i] : 0,
+			                 in->sock != NULL, in->sock ? in->sock[i] : 0);
+		}
+		out->src_off[j] = r.src_off;
+		out->len[j] = (uint16_t)r.len;
+		out->kind[j] = (uint8_t)r.kind;
+		if (out->meta)
+			memcpy(&out->meta[j], r.meta, sizeof(out->meta[j]));
+		out->dst_off[j] = at;
+		at += gcl_pay_pad(r.len, amask);
+		c[gcl_pay_counter(r.kind)]++;
+		c[GCL_PAYC_BYTES] += r.len;
+	}
+	*out->total = at;
+	if (in->seg_off)
+		for (uint64_t s = 0; s <= in->nseg; s++)
+			out->seg_bytes[s] = in->seg_off[s] < in->m ? out->dst_off[in->seg_off[s]] : at;
+	if (counts)
+		for (int k = 0; k < GCL_PAYC_NR; k++)
 			counts[k] += c[k];
 	return 0;
 }

@@ -61,6 +61,14 @@ L4_NA, L4_GOOD, L4_BAD, L4_NONE, L4_FILLED_IP, L4_FILLED_L4 = 0, 1, 2, 3, 0x10, 
 L4C_NR = 8
 # its launch (csrc/gcl_l4.hip): lanes per block, and the grid's cap
 L4_THREADS, L4_BLOCKS_PER_CU = 256, 7
+# gcl_l4_payload: the kind byte, the counter slots, the cap on blocks, struct gcl_pay_meta
+PAY_NA, PAY_UDP, PAY_TCP, PAY_NOSOCK, PAY_BADCSUM, PAY_OOR = range(6)
+(PAYC_UDP, PAYC_TCP, PAYC_NA, PAYC_NOSOCK, PAYC_BADCSUM, PAYC_OOR, PAYC_BYTES) = range(7)
+PAYC_NR, PAY_MAX_BLOCKS = 8, 1024
+# its launches (csrc/gcl_payload.hip): entries per tile, and the library's ranges per CU
+PAY_TILE, PAY_BLOCKS_PER_CU = 256, 4
+PAY_META_DTYPE = np.dtype([("rip", "<u4"), ("rport", "<u2"), ("proto", "u1"), ("tcp_flags", "u1"),
+                           ("seq", "<u4"), ("ack", "<u4")])
 # gcl_sock_lookup: entry kinds, the answers that are not cookies, the counter slots
 SOCK_MATCH_3TUPLE, SOCK_MATCH_5TUPLE, SOCK_MAX_ENTRIES = 3, 5, 1 << 20
 SOCK_NA, SOCK_MISS, SOCK_MULTI, SOCK_COOKIE_MAX = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFEF
@@ -263,6 +271,21 @@ class GclL4In(ctypes.Structure):
                 ("len_hint", ctypes.c_uint32), ("tx_olflags", ctypes.c_void_p)]
 
 
+class GclPayIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("align", ctypes.c_uint32), ("order", ctypes.c_void_p),
+                ("m", ctypes.c_uint64), ("sock", ctypes.c_void_p), ("l4_status", ctypes.c_void_p),
+                ("seg_off", ctypes.c_void_p), ("nseg", ctypes.c_uint32), ("blocks", ctypes.c_uint32)]
+
+
+class GclPayOut(ctypes.Structure):
+    _fields_ = [("src_off", ctypes.c_void_p), ("len", ctypes.c_void_p), ("dst_off", ctypes.c_void_p),
+                ("kind", ctypes.c_void_p), ("meta", ctypes.c_void_p), ("seg_bytes", ctypes.c_void_p),
+                ("total", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(GclPayIn) == 56 and ctypes.sizeof(GclPayOut) == 56 and PAY_META_DTYPE.itemsize == 16
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} missing: run `python caladan_amd/build.py` "
@@ -335,6 +358,11 @@ def _load():
         "gcl_rx_csum_flags": (ctypes.c_uint8, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint8]),
         "gcl_l4_csum": (i32, [vp, ctypes.POINTER(GclBatch), ctypes.POINTER(GclL4In), vp, vp, vp]),
         "gcl_l4_csum_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclL4In), vp, vp]),
+        "gcl_l4_payload_workspace": (i32, [u64, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_l4_payload": (i32, [vp, ctypes.POINTER(GclBatch), ctypes.POINTER(GclPayIn),
+                                 ctypes.POINTER(GclPayOut), vp, vp, ctypes.c_size_t, vp]),
+        "gcl_l4_payload_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclPayIn),
+                                      ctypes.POINTER(GclPayOut), vp]),
         "gcl_sock_set": (i32, [vp, ctypes.c_uint16, vp, u32]),
         "gcl_sock_lookup": (i32, [vp, ctypes.POINTER(GclBatch), vp, vp, vp, vp]),
         "gcl_sock_tbl_new": (vp, []),
@@ -515,6 +543,80 @@ def l4_csum_host(frames, pkt_len, mode=L4_VERIFY, stride=0, offs=None, n=None, f
     _check(lib.gcl_l4_csum_host(ctypes.byref(b), ctypes.byref(lin), _ptr(status), _ptr(counts)),
            "gcl_l4_csum_host")
     return status
+
+
+PAY_OUT_FIELDS = ("src_off", "len", "dst_off", "kind", "meta", "seg_bytes", "total")
+
+
+def _pay_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status, seg_off,
+                 nseg, align, blocks, out, counts):
+    """The three structs of gcl_l4_payload / gcl_l4_payload_host, sizes
+    checked; @out maps PAY_OUT_FIELDS to buffers (meta and seg_bytes may be
+    None)."""
+    for arr, w in ((offs, 8), (pkt_len, 2), (sock, 4), (l4_status, 1)):
+        if arr is not None and _nbytes(arr) < w * n:
+            raise ValueError("per-packet array too small")
+    for arr, w in ((order, 4), (out["src_off"], 8), (out["len"], 2), (out["dst_off"], 8),
+                   (out["kind"], 1), (out["meta"], 16)):
+        if arr is not None and _nbytes(arr) < w * m:
+            raise ValueError("per-entry array too small")
+    if seg_off is not None and _nbytes(seg_off) < 4 * (nseg + 1):
+        raise ValueError("seg_off too small")
+    if out["seg_bytes"] is not None and _nbytes(out["seg_bytes"]) < 8 * (nseg + 1):
+        raise ValueError("seg_bytes too small")
+    if out["total"] is not None and _nbytes(out["total"]) < 8:
+        raise ValueError("total too small")
+    if counts is not None and _nbytes(counts) < 8 * PAYC_NR:
+        raise ValueError("counts buffer too small")
+    b = GclBatch(frames=_ptr(frames), frames_len=_frames_len(frames, frames_len), stride=stride,
+                 offs=_ptr(offs), olflags=None, rss=None, fdir_hi=None, pkt_len=_ptr(pkt_len), n=n,
+                 dst_hint=None)
+    pin = GclPayIn(size=ctypes.sizeof(GclPayIn), align=align, order=_ptr(order), m=m, sock=_ptr(sock),
+                   l4_status=_ptr(l4_status), seg_off=_ptr(seg_off), nseg=nseg, blocks=blocks)
+    pout = GclPayOut(**{f: _ptr(out[f]) for f in PAY_OUT_FIELDS})
+    return b, pin, pout
+
+
+def _pay_m(n, m, order):
+    if m is not None:
+        return m
+    if order is None:
+        return n
+    if not (hasattr(order, "numel") or isinstance(order, np.ndarray)):
+        raise ValueError("m is required when order is a raw address")
+    return order.numel() if hasattr(order, "numel") else len(order)
+
+
+def l4_payload_host(frames, pkt_len, stride=0, offs=None, n=None, frames_len=None, order=None, m=None,
+                    sock=None, l4_status=None, seg_off=None, nseg=None, align=0, blocks=0, out=None,
+                    counts=None):
+    """gcl_l4_payload_host: the rule of Classifier.l4_payload on the CPU over
+    numpy arrays.  @out maps PAY_OUT_FIELDS to arrays (u64, u16, u64, u8,
+    PAY_META_DTYPE, u64[nseg + 1], u64[1]); the ones left out are allocated
+    (meta too; seg_bytes only with @seg_off).  @counts is a u64[PAYC_NR],
+    accumulated.  Returns the dict."""
+    n = len(pkt_len) if n is None else n
+    m = _pay_m(n, m, order)
+    nseg = (len(seg_off) - 1 if seg_off is not None else 0) if nseg is None else nseg
+    out = dict(out or {})
+    for f, dt, k in (("src_off", np.uint64, m), ("len", np.uint16, m), ("dst_off", np.uint64, m),
+                     ("kind", np.uint8, m), ("meta", PAY_META_DTYPE, m), ("total", np.uint64, 1)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    if "seg_bytes" not in out:
+        out["seg_bytes"] = np.zeros(nseg + 1, dtype=np.uint64) if seg_off is not None else None
+    b, pin, pout = _pay_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status,
+                                seg_off, nseg, align, blocks, out, counts)
+    _check(lib.gcl_l4_payload_host(ctypes.byref(b), ctypes.byref(pin), ctypes.byref(pout), _ptr(counts)),
+           "gcl_l4_payload_host")
+    return out
+
+
+def l4_payload_workspace(m, blocks=0):
+    """gcl_l4_payload_workspace: bytes of device scratch a call over @m entries takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_l4_payload_workspace(m, blocks, ctypes.byref(need)), "gcl_l4_payload_workspace")
+    return need.value
 
 
 def sock_entries(entries):
@@ -992,6 +1094,47 @@ class Classifier:
         _check(lib.gcl_l4_csum(self._ctx, ctypes.byref(b), ctypes.byref(lin), _ptr(status),
                                _ptr(counts), stream), "gcl_l4_csum")
         return status
+
+    def l4_payload(self, frames, n, pkt_len, stride=0, offs=None, frames_len=None, order=None, m=None,
+                   sock=None, l4_status=None, seg_off=None, nseg=None, align=0, blocks=0, out=None,
+                   counts=None, workspace=None, stream=None):
+        """gcl_l4_payload: the payload descriptors and the packed receive
+        layout of the list @order[0..m) (None: every packet in turn) on the
+        GPU, asynchronous.  @pkt_len is required; @sock and @l4_status are
+        what sock_lookup and l4_csum(L4_VERIFY) wrote; @seg_off (int32,
+        u32[nseg + 1]) is e.g. a plan's bucket_off.  @out maps PAY_OUT_FIELDS
+        to device buffers; the ones left out are allocated on @frames' device
+        (src_off, dst_off, seg_bytes and total int64, len int16, kind uint8,
+        meta uint8[m, 16]; seg_bytes only with @seg_off).  @counts is a device
+        u64[PAYC_NR], accumulated.  The scratch is @workspace, or a torch
+        tensor kept on the classifier.  Returns the dict: src_off, len and
+        dst_off are copy_batch's src_off, length and dst_off."""
+        import torch
+        if pkt_len is None:
+            raise ValueError("pkt_len is required")
+        m = _pay_m(n, m, order)
+        nseg = (seg_off.numel() - 1 if seg_off is not None else 0) if nseg is None else nseg
+        dev = frames.device if hasattr(frames, "device") else None
+        out = dict(out or {})
+        for f, dt, shape in (("src_off", torch.int64, (max(m, 1),)), ("len", torch.int16, (max(m, 1),)),
+                             ("dst_off", torch.int64, (max(m, 1),)), ("kind", torch.uint8, (max(m, 1),)),
+                             ("meta", torch.uint8, (max(m, 1), 16)), ("total", torch.int64, (1,))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        if "seg_bytes" not in out:
+            out["seg_bytes"] = torch.empty(nseg + 1, dtype=torch.int64, device=dev) \
+                if seg_off is not None else None
+        b, pin, pout = _pay_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock,
+                                    l4_status, seg_off, nseg, align, blocks, out, counts)
+        ws = workspace
+        if ws is None:
+            need = l4_payload_workspace(m, blocks)
+            ws = getattr(self, "_pay_ws", None)
+            if ws is None or ws.numel() < need or ws.device != out["total"].device:
+                ws = self._pay_ws = torch.empty(need, dtype=torch.uint8, device=out["total"].device)
+        _check(lib.gcl_l4_payload(self._ctx, ctypes.byref(b), ctypes.byref(pin), ctypes.byref(pout),
+                                  _ptr(counts), _ptr(ws), _nbytes(ws), stream), "gcl_l4_payload")
+        return out
 
     def sock_set(self, uniqid, entries):
         """gcl_sock_set: replace runtime @uniqid's socket entries (sock_entries

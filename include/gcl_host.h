@@ -125,6 +125,22 @@ int gcl_l4_csum_host(const struct gcl_batch *b, const struct gcl_l4_in *in, uint
                      uint64_t *counts);
 
 /*
+ * gcl_l4_payload_host - the rule of gcl_l4_payload (gclassify.h) on the CPU
+ * over host pointers, for the batches the GPU did not see: what udp_conn_recv
+ * and tcp_rx_conn find out about each datagram of a list (runtime/net/udp.c:
+ * 79-107, runtime/net/tcp_in.c:182-218) and the dense layout of the kept
+ * payloads, sequential plain C with no workspace.  @b, @in and @out are
+ * gcl_l4_payload's structs with every pointer a host pointer (in->blocks is
+ * checked against GCL_PAY_MAX_BLOCKS and otherwise not looked at); @counts is
+ * a host u64[GCL_PAYC_NR], ACCUMULATED, may be NULL.  The same outputs, the
+ * same counts and the same guarantee.  0, or -EINVAL for what gcl_l4_payload
+ * refuses (the ctx and the workspace apart).  m == 0 writes *total = 0 and
+ * zero seg_bytes, and nothing else.
+ */
+int gcl_l4_payload_host(const struct gcl_batch *b, const struct gcl_pay_in *in,
+                        const struct gcl_pay_out *out, uint64_t *counts);
+
+/*
  * The socket table of gcl_sock_set / gcl_sock_lookup (gclassify.h) as a
  * host-only object: the same entry checks, the same table image and the same
  * probe (one shared inline function), with no GPU.  A context embeds one.

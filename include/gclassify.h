@@ -1230,6 +1230,128 @@ enum {
 int gcl_sock_lookup(struct gcl_ctx *ctx, const struct gcl_batch *b, const void *verdicts,
                     uint32_t *sock, uint64_t *counts, void *hip_stream);
 
+/*
+ * Payload descriptors and a packed receive layout: the step that ends the
+ * receive path in the reference.  Once trans_lookup has an entry,
+ * udp_conn_recv / udp_par_recv pull the 8-byte UDP header and hand on
+ * mbuf_data, mbuf_length -- frame bytes [42, 14 + tot) after net_rx_one's trim
+ * (runtime/net/udp.c:79-107, :811-840, runtime/net/core.c:283-287);
+ * tcp_rx_conn reads seq, ack, the flags and hdr_len = off * 4, drops
+ * hdr_len < 20 and takes len = tot - 20 - hdr_len bytes behind the header
+ * (runtime/net/tcp_in.c:182-218); udp_read_from / tcp_read then memcpy those
+ * bytes into the application's buffer on a runtime core (udp.c:373-379).
+ * gcl_l4_payload says, for every entry of a list of packets, where the
+ * payload starts, how long it is and where it goes in a dense receive buffer:
+ * the src_off[], len[] and dst_off[] that gcl_copy_batch takes, so that the
+ * chain classify -> sock_lookup -> l4_csum VERIFY -> plan -> l4_payload ->
+ * copy_batch leaves, per runtime, one dense payload stream in HBM plus a
+ * descriptor per datagram.  tcp_rx_conn's state machine (sequence checks,
+ * reassembly, ACKs) stays with the runtime: meta[] carries what it reads.
+ *
+ * List entry j names packet i = in->order ? in->order[j] : j.  Packet i has
+ * o, avail and L = min(b->pkt_len[i], avail) exactly as gcl_l4_csum defines
+ * them, and is L4-eligible exactly as there (b->pkt_len is REQUIRED).  The
+ * first line that matches decides:
+ *   i >= b->n                                              GCL_PAY_OOR
+ *   the packet is not L4-eligible                          GCL_PAY_NA
+ *   TCP with hl = 4 * (byte 46 >> 4), when hl < 20 or
+ *     hl > tot - 20 (UDP has hl = 8)                       GCL_PAY_NA
+ *   in->l4_status given and (l4_status[i] & 0xF) ==
+ *     GCL_L4_BAD (the FILLED bits are ignored)             GCL_PAY_BADCSUM
+ *   in->sock given and sock[i] > GCL_SOCK_COOKIE_MAX
+ *     (NA, MISS, MULTI, the reserved values)               GCL_PAY_NOSOCK
+ *   otherwise the entry is KEPT: kind[j] is GCL_PAY_UDP or GCL_PAY_TCP,
+ *     len[j] = tot - 20 - hl (it may be 0: a pure ACK, an empty datagram),
+ *     src_off[j] = o + 34 + hl, an offset into b->frames that lies inside
+ *     [o, o + L] and is directly usable as gcl_copy_in.src_off, and meta[j]
+ *     is filled from the frame.
+ * Every entry that is not kept gets len = 0, src_off = 0 and an all-zero meta
+ * (proto 0).
+ *
+ * The layout, with pad(x) = x rounded up to in->align (0 or 1: dense):
+ *   dst_off[j]   = the sum of pad(len[j']) over j' < j
+ *   *total       = that sum over all m entries
+ *   seg_bytes[s] = seg_off[s] < m ? dst_off[seg_off[s]] : *total, s <= nseg
+ * With a plan's order and seg_off = its bucket_off (nseg = nbuckets),
+ * runtime r's stream is therefore bytes [seg_bytes[r], seg_bytes[r + 1]) of
+ * the receive buffer.  Garbage in seg_off gives garbage values, never a read
+ * out of range.  The copy that follows is
+ *   gcl_copy_in  { .src = b->frames, .src_len = b->frames_len,
+ *                  .src_off = out->src_off, .len = out->len, .n = m }
+ *   gcl_copy_out { .dst_off = out->dst_off, ... }.
+ *
+ * Every pointer is a device pointer; each array is aligned to its element,
+ * meta to 16 B.  @counts is a device u64[GCL_PAYC_NR], ACCUMULATED, may be
+ * NULL: per call the six kind counters sum to m, and BYTES adds the unpadded
+ * len of every entry.  Frames are addressed as gcl_rx_csum addresses them;
+ * rss, fdir_hi, dst_hint and olflags are ignored.
+ *
+ * Guarantee: no content of frames, offs, pkt_len, order, sock, l4_status or
+ * seg_off causes a read outside frames[0, frames_len) or the given arrays
+ * (order[0, m), seg_off[0, nseg], the n-element per-packet arrays), or a
+ * write outside the m-element outputs, seg_bytes[0, nseg], total and counts.
+ *
+ * gcl_l4_payload_workspace - bytes of device scratch a call takes: one u64
+ *   per contiguous range the list is cut into (in->blocks of them, or the
+ *   cap GCL_PAY_MAX_BLOCKS when in->blocks is 0).  -EINVAL for a NULL @bytes,
+ *   m > 2^31 or blocks > GCL_PAY_MAX_BLOCKS.
+ * gcl_l4_payload - asynchronous on @hip_stream: three launches (four with
+ *   seg_off), none of which waits for another block.  No allocation, no host
+ *   synchronisation.  @workspace (device, 16-B aligned) need not be zeroed and
+ *   may be reused by the next call on the same stream.  m == 0 writes
+ *   *total = 0 and zero seg_bytes, and nothing else.  -EINVAL for a NULL ctx,
+ *   b, in or out; a wrong in->size; an align that is not 0 or a power of two
+ *   <= 256; order == NULL with m != b->n; m > 2^31; a NULL src_off, len,
+ *   dst_off, kind or total; seg_off without seg_bytes or seg_bytes without
+ *   seg_off; any given array that is not aligned to its element (meta: 16 B);
+ *   blocks > GCL_PAY_MAX_BLOCKS; a NULL workspace, one that is not 16-B
+ *   aligned or one smaller than gcl_l4_payload_workspace says; and, when
+ *   m > 0, a NULL or misaligned b->pkt_len and the batches gcl_rx_csum
+ *   refuses.  -EIO when a launch fails.
+ */
+/* kind[j] */
+#define GCL_PAY_NA      0  /* not a datagram this call describes */
+#define GCL_PAY_UDP     1
+#define GCL_PAY_TCP     2
+#define GCL_PAY_NOSOCK  3  /* in->sock given and sock[i] > GCL_SOCK_COOKIE_MAX */
+#define GCL_PAY_BADCSUM 4  /* in->l4_status given and (l4_status[i] & 0xF) == GCL_L4_BAD */
+#define GCL_PAY_OOR     5  /* order[j] >= n */
+#define GCL_PAY_MAX_BLOCKS 1024  /* the cap on in->blocks */
+enum { GCL_PAYC_UDP = 0, GCL_PAYC_TCP, GCL_PAYC_NA, GCL_PAYC_NOSOCK, GCL_PAYC_BADCSUM,
+       GCL_PAYC_OOR, GCL_PAYC_BYTES, GCL_PAYC_NR = 8 };
+struct gcl_pay_meta {            /* 16 B, host order */
+	uint32_t rip;                /* the sender: frame bytes 26-29 */
+	uint16_t rport;              /* bytes 34-35 */
+	uint8_t  proto;              /* 6 or 17; 0: the entry is not kept */
+	uint8_t  tcp_flags;          /* byte 47, 0 for UDP */
+	uint32_t seq, ack;           /* TCP bytes 38-41, 42-45; 0 for UDP */
+};
+struct gcl_pay_in {
+	uint32_t size, align;        /* sizeof(struct gcl_pay_in); align: 0 or 1 = dense, else a
+	                                power of two <= 256 */
+	const uint32_t *order;       /* optional u32[m]; NULL: m == b->n and i = j */
+	uint64_t m;                  /* list entries, <= 2^31 */
+	const uint32_t *sock;        /* optional u32[n], as gcl_sock_lookup wrote it */
+	const uint8_t  *l4_status;   /* optional u8[n], as GCL_L4_VERIFY wrote it */
+	const uint32_t *seg_off;     /* optional u32[nseg + 1], e.g. a plan's bucket_off */
+	uint32_t nseg;
+	uint32_t blocks;             /* 0: the library's choice; else the number of contiguous
+	                                list ranges the scan is cut into (tests) */
+};
+struct gcl_pay_out {             /* device; m entries each, aligned to their element */
+	uint64_t *src_off;           /* required */
+	uint16_t *len;               /* required */
+	uint64_t *dst_off;           /* required */
+	uint8_t  *kind;              /* required */
+	struct gcl_pay_meta *meta;   /* optional, 16-B aligned */
+	uint64_t *seg_bytes;         /* u64[nseg + 1], required iff seg_off */
+	uint64_t *total;             /* u64[1], required */
+};
+int gcl_l4_payload_workspace(uint64_t m, uint32_t blocks, size_t *bytes);
+int gcl_l4_payload(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct gcl_pay_in *in,
+                   const struct gcl_pay_out *out, uint64_t *counts,
+                   void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
