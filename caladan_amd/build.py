@@ -3,7 +3,7 @@
 hipcc compiles the HIP kernels + C ABI (csrc/gcl_*.hip: the context, the
 batch kernels, the persistent rx loop, the transports and allocation, the
 generator); gcc compiles the host-side C (csrc/gcl_host.c, csrc/gcl_pcap.c,
-csrc/gcl_sock.c);
+csrc/gcl_sock.c, csrc/gcl_neigh.c);
 hipcc links them into caladan_amd/libgclassify.so.  The multi-GPU group (csrc/gcl_group.hip,
 include/gcl_group.h) is its own library, caladan_amd/libgclgroup.so, linked
 against libgclassify.so and RCCL, so that a single-GPU dataplane does not
@@ -26,9 +26,10 @@ ARCH = os.environ.get("GCL_OFFLOAD_ARCH", "gfx950")
 
 SOURCES_HIP = ["gcl_ctx.hip", "gcl_batch.hip", "gcl_loop.hip", "gcl_xfer.hip", "gcl_gen.hip",
                "gcl_plan.hip", "gcl_pack.hip", "gcl_csum.hip", "gcl_copy.hip", "gcl_sock.hip", "gcl_l4.hip",
-               "gcl_payload.hip"]
-SOURCES_C = ["gcl_host.c", "gcl_pcap.c", "gcl_sock.c"]
-DEPS = ["gcl_device.h", "gcl_kern.h", "gcl_ctx.h", "gcl_sock.h", "gcl_pay.h", "../../include/gclassify.h",
+               "gcl_payload.hip", "gcl_txhdr.hip"]
+SOURCES_C = ["gcl_host.c", "gcl_pcap.c", "gcl_sock.c", "gcl_neigh.c"]
+DEPS = ["gcl_device.h", "gcl_kern.h", "gcl_ctx.h", "gcl_sock.h", "gcl_pay.h", "gcl_neigh.h", "gcl_txh.h",
+        "../../include/gclassify.h",
         "../../include/gcl_host.h", "../../include/gcl_pcap.h"]
 SOURCE_GROUP = "gcl_group.hip"
 DEPS_GROUP = ["../../include/gclassify.h", "../../include/gcl_group.h"]
@@ -229,6 +230,24 @@ def build_sanitized_pay(out_dir=None):
     return exe
 
 
+def build_sanitized_txh(out_dir=None):
+    """The ASan + UBSan host build of csrc/gcl_host.c (gcl_tx_hdr_host, with
+    the rule of csrc/gcl_txh.h that the GPU kernel shares) and of
+    csrc/gcl_neigh.c (the neighbour table, its placement and the probe of
+    csrc/gcl_neigh.h), linked into tests/fuzz/txh_fuzz.c: a stand-alone driver
+    over exactly sized heap regions with hostile descriptors, offsets, caps
+    and table images.  Returns the driver's path."""
+    out_dir = out_dir or os.path.join(ROOT, "build", "sanitize")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "txh_fuzz")
+    srcs = [os.path.join(ROOT, "tests", "fuzz", "txh_fuzz.c"), os.path.join(CSRC, "gcl_host.c"),
+            os.path.join(CSRC, "gcl_neigh.c")]
+    if _stale(exe, srcs + [os.path.join(CSRC, d) for d in DEPS]):
+        _run(["gcc", "-std=gnu11", "-Wall", "-Wno-unused-parameter", *SANITIZE_FLAGS,
+              "-o", exe, *srcs, "-lm"])
+    return exe
+
+
 if __name__ == "__main__":
     if "--sanitize" in sys.argv:
         print(build_sanitized())
@@ -239,5 +258,6 @@ if __name__ == "__main__":
         print(build_sanitized_sock())
         print(build_sanitized_l4())
         print(build_sanitized_pay())
+        print(build_sanitized_txh())
     else:
         build(force="--force" in sys.argv, verbose_resources="--resources" in sys.argv)

@@ -76,6 +76,22 @@ struct gcl_ctx {
 		hipStream_t users[gclk::kImgUsers];
 		bool many;           /* more of them than users[] holds */
 	} sockdev;
+	/* the neighbour table (gcl_txhdr.hip): the host object, created by the
+	 * first gcl_neigh_set or gcl_tx_hdr, and its device copy, which starts
+	 * with the Toeplitz LUT of cfg.rss_key (kToepBytes) whatever hash_mode is.
+	 * Handled like the socket table and independent of it. */
+	struct gcl_neigh_tbl *neigh;
+	struct NeighDev {
+		uint8_t *dimg;       /* LUT | table image */
+		uint8_t *staging;    /* pinned, as large */
+		size_t cap;
+		uint32_t lg, seed, bits; /* of the image on the device */
+		hipEvent_t copied;
+		hipStream_t up_stream;
+		int nusers;
+		hipStream_t users[gclk::kImgUsers];
+		bool many;
+	} neighdev;
 	int cur;
 	hipStream_t last_stream;
 	/* profiling */
@@ -108,6 +124,9 @@ inline int32_t tuned(int32_t v, int32_t dflt) { return v == GCL_TUNE_AUTO ? dflt
 /* gcl_sock.hip */
 void sock_runtime_del(gcl_ctx *c, uint16_t uniqid); /* gcl_runtime_del: drop its entries */
 void sock_close(gcl_ctx *c);                        /* gcl_close: free the table and its copy */
+
+/* gcl_txhdr.hip */
+void neigh_close(gcl_ctx *c);                       /* gcl_close: free the table and its copy */
 
 /* gcl_xfer.hip: device address of pinned / registered host memory, or NULL */
 void *mapped(const void *h);

@@ -72,6 +72,8 @@ extern "C" int gcl_open(int hip_device, const struct gcl_cfg *cfg, struct gcl_ct
 	c->cur = 0;
 	c->sock = nullptr;
 	memset(&c->sockdev, 0, sizeof(c->sockdev));
+	c->neigh = nullptr;
+	memset(&c->neighdev, 0, sizeof(c->neighdev));
 	c->last_stream = nullptr;
 	c->prof_ms = 0;
 	c->prof_launches = 0;
@@ -118,6 +120,7 @@ extern "C" void gcl_close(struct gcl_ctx *c)
 		gcl_rxloop_stop(c->loop);
 	(void)hipDeviceSynchronize();
 	sock_close(c);
+	neigh_close(c);
 	for (int i = 0; i < 2; i++) {
 		(void)hipFree(c->dimg[i]);
 		for (int j = 0; j < kImgUsers; j++)

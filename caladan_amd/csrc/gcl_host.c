@@ -9,6 +9,7 @@
 #include "../../include/gcl_host.h"
 #include "../../include/gclassify.h"
 #include "gcl_pay.h"
+#include "gcl_txh.h"
 
 #define ROT(x, k) (((x) << (k)) | ((x) >> (32 - (k))))
 
@@ -432,6 +433,66 @@ int gcl_l4_payload_host(const struct gcl_batch *b, const struct gcl_pay_in *in,
 			out->seg_bytes[s] = in->seg_off[s] < in->m ? out->dst_off[in->seg_off[s]] : at;
 	if (counts)
 		for (int k = 0; k < GCL_PAYC_NR; k++)
+			counts[k] += c[k];
+	return 0;
+}
+
+/* The rule of gcl_tx_hdr (gclassify.h) on the CPU: gcl_txh_rule of gcl_txh.h
+ * for every entry in turn, the header bytes it names stored with memcpy. */
+int gcl_tx_hdr_host(const struct gcl_neigh_tbl *tbl, const uint8_t rss_key[40],
+                    const struct gcl_txh_in *in, const struct gcl_txh_out *out, uint64_t *counts)
+{
+	static const struct gcl_neigh_slot none[1 + (2u << 3)]; /* an empty image: header | 8 buckets */
+	uint64_t c[GCL_TXHC_NR] = {0};
+
+	if (!rss_key || !in || !out || in->size != sizeof(*in) || in->m > (1ull << 31))
+		return -EINVAL;
+	if (in->m == 0)
+		return 0;
+	if (!in->desc || !in->frame_off || !in->frames || in->frames_len == UINT64_MAX || !out->cmd ||
+	    !out->payload || !out->pkt_len || !out->tx_olflags || !out->status)
+		return -EINVAL;
+	const struct gcl_neigh_view v = tbl ? gcl_neigh_tbl_view(tbl) : gcl_neigh_view_of(3, 0, 32, none);
+
+	for (uint64_t j = 0; j < in->m; j++) {
+		uint32_t d[8], hash = 0;
+		uint64_t o;
+		uint8_t h[56];
+
+		memcpy(d, (const uint8_t *)in->desc + 32 * j, 32); /* little-endian host */
+		memcpy(&o, (const uint8_t *)in->frame_off + 8 * j, 8);
+		const struct gcl_txh_res r = gcl_txh_rule(&v, &in->net, d, o, in->frames_len, in->cap);
+		if (r.status != GCL_TXH_REFUSED) {
+			uint8_t *f = in->frames + o;
+			memcpy(h, r.w, sizeof(h));
+			memcpy(f + 14, h + 14, r.l4end - 14);
+			if (r.eth) {
+				memcpy(f, h, 14);
+				if (r.pkt_len > r.len)
+					memset(f + r.len, 0, r.pkt_len - r.len);
+			}
+		}
+		if (r.local) { /* do_toeplitz(netcfg.addr, daddr, sport, dport), core.c:730 */
+			const uint32_t a = in->net.addr;
+			const uint8_t t[12] = { a >> 24, a >> 16, a >> 8, a, r.nh >> 24, r.nh >> 16, r.nh >> 8, r.nh,
+			                        r.lport >> 8, r.lport, r.rport >> 8, r.rport };
+			hash = gcl_toeplitz(rss_key, 40, t, 12);
+		}
+		const uint64_t cmd = gcl_txh_cmd(&r), pay = gcl_txh_payload(&r, in->shm_base, o, hash);
+		const uint16_t pl = (uint16_t)r.pkt_len;
+		memcpy((uint8_t *)out->cmd + 8 * j, &cmd, 8);
+		memcpy((uint8_t *)out->payload + 8 * j, &pay, 8);
+		memcpy((uint8_t *)out->pkt_len + 2 * j, &pl, 2);
+		out->tx_olflags[j] = (uint8_t)r.olflags;
+		if (out->hash)
+			memcpy((uint8_t *)out->hash + 4 * j, &hash, 4);
+		out->status[j] = (uint8_t)r.status;
+		c[r.status]++;
+		c[GCL_TXHC_LOCAL] += r.local;
+		c[GCL_TXHC_BYTES] += r.status == GCL_TXH_OK ? r.pkt_len : 0;
+	}
+	if (counts)
+		for (int k = 0; k < GCL_TXHC_NR; k++)
 			counts[k] += c[k];
 	return 0;
 }

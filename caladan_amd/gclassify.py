@@ -78,6 +78,19 @@ SOCK_BLOCK_PKTS, SOCK_BLOCKS_PER_CU = 256, 4
 # struct gcl_sock_entry as a numpy record
 SOCK_ENTRY_DTYPE = np.dtype([("lip", "<u4"), ("rip", "<u4"), ("lport", "<u2"), ("rport", "<u2"),
                              ("proto", "u1"), ("match", "u1"), ("pad", "<u2"), ("cookie", "<u4")])
+# gcl_tx_hdr: the status byte, the counter slots, gcl_txh_net.flags, the txpkt olflags it writes
+TXH_OK, TXH_SELF, TXH_NONEIGH, TXH_REFUSED = range(4)
+(TXHC_OK, TXHC_SELF, TXHC_NONEIGH, TXHC_REFUSED, TXHC_LOCAL, TXHC_BYTES) = range(6)
+TXHC_NR, TXH_IP_CSUM, NEIGH_MAX_ENTRIES = 8, 0x01, 1 << 16
+OLFLAG_IP_CHKSUM, OLFLAG_TCP_CHKSUM, OLFLAG_IPV4, TXFLAG_LOCAL, TXFLAG_LOCAL_HINT = 0x01, 0x02, 0x04, 0x10, 0x40
+# its launch (csrc/gcl_txhdr.hip): entries a block takes per pass, and the grid's cap
+TXH_BLOCK_PKTS, TXH_BLOCKS_PER_CU = 256, 4
+# struct gcl_txh_desc and struct gcl_neigh_entry as numpy records
+TXH_DESC_DTYPE = np.dtype([("lip", "<u4"), ("rip", "<u4"), ("lport", "<u2"), ("rport", "<u2"),
+                           ("proto", "u1"), ("tcp_flags", "u1"), ("tcp_off", "u1"), ("ecn", "u1"),
+                           ("seq", "<u4"), ("ack", "<u4"), ("win", "<u2"), ("paylen", "<u2"),
+                           ("pad", "<u4")])
+NEIGH_ENTRY_DTYPE = np.dtype([("ip", "<u4"), ("mac", "u1", (6,)), ("pad", "<u2")])
 STAT_NAMES = ["RX_UNREGISTERED_MAC", "RX_UNICAST_FAIL", "RX_BROADCAST_FAIL",
               "RX_FLOW_TAG_MATCH", "RX_UNHANDLED", "RX_HASH_MISSING", "RX_PULLED"]
 
@@ -283,6 +296,25 @@ class GclPayOut(ctypes.Structure):
                 ("total", ctypes.c_void_p)]
 
 
+class GclTxhNet(ctypes.Structure):
+    _fields_ = [("addr", ctypes.c_uint32), ("netmask", ctypes.c_uint32), ("gateway", ctypes.c_uint32),
+                ("mac", ctypes.c_uint8 * 6), ("min_pkt_size", ctypes.c_uint8), ("flags", ctypes.c_uint8)]
+
+
+class GclTxhIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("desc", ctypes.c_void_p),
+                ("frame_off", ctypes.c_void_p), ("m", ctypes.c_uint64), ("frames", ctypes.c_void_p),
+                ("frames_len", ctypes.c_uint64), ("shm_base", ctypes.c_uint64), ("cap", ctypes.c_uint32),
+                ("pad2", ctypes.c_uint32), ("net", GclTxhNet)]
+
+
+class GclTxhOut(ctypes.Structure):
+    _fields_ = [("cmd", ctypes.c_void_p), ("payload", ctypes.c_void_p), ("pkt_len", ctypes.c_void_p),
+                ("tx_olflags", ctypes.c_void_p), ("hash", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(GclTxhIn) == 88 and ctypes.sizeof(GclTxhNet) == 20 and TXH_DESC_DTYPE.itemsize == 32
+assert NEIGH_ENTRY_DTYPE.itemsize == 12
 assert ctypes.sizeof(GclPayIn) == 56 and ctypes.sizeof(GclPayOut) == 56 and PAY_META_DTYPE.itemsize == 16
 
 
@@ -372,6 +404,16 @@ def _load():
         "gcl_sock_tbl_hash_bits": (i32, [vp, u32]),
         "gcl_sock_tbl_lookup_host": (i32, [vp, ctypes.c_uint8, ctypes.c_uint8, u32,
                                            ctypes.POINTER(GclBatch), vp, vp, vp]),
+        "gcl_neigh_set": (i32, [vp, vp, u32]),
+        "gcl_tx_hdr": (i32, [vp, ctypes.POINTER(GclTxhIn), ctypes.POINTER(GclTxhOut), vp, vp]),
+        "gcl_tx_hdr_host": (i32, [vp, ctypes.c_char_p, ctypes.POINTER(GclTxhIn), ctypes.POINTER(GclTxhOut),
+                                  vp]),
+        "gcl_neigh_tbl_new": (vp, []),
+        "gcl_neigh_tbl_free": (None, [vp]),
+        "gcl_neigh_tbl_set": (i32, [vp, vp, u32]),
+        "gcl_neigh_tbl_hash_bits": (i32, [vp, u32]),
+        "gcl_neigh_tbl_count": (u32, [vp]),
+        "gcl_neigh_tbl_lookup": (i32, [vp, u32, ctypes.POINTER(ctypes.c_uint8 * 6)]),
         "gcl_copy_batch": (i32, [vp, ctypes.POINTER(GclCopyIn), ctypes.POINTER(GclCopyOut), vp, vp]),
         "gcl_copy_batch_host": (i32, [ctypes.POINTER(GclCopyIn), ctypes.POINTER(GclCopyOut), vp]),
         "gcl_host_deliver_packed": (u64, [vp, u32, vp, i32, vp, vp, vp, vp, u64, u64, vp,
@@ -688,6 +730,111 @@ class SockTable:
                                             _ptr(verdicts), _ptr(sock), _ptr(counts)),
                "gcl_sock_tbl_lookup_host")
         return sock[:n], counts
+
+
+def neigh_entries(entries):
+    """struct gcl_neigh_entry[n] as a numpy record array (NEIGH_ENTRY_DTYPE):
+    @entries is such an array already, or a sequence of (ip, mac) pairs, mac
+    six bytes."""
+    if isinstance(entries, np.ndarray):
+        if entries.dtype != NEIGH_ENTRY_DTYPE:
+            raise ValueError("entries: not NEIGH_ENTRY_DTYPE")
+        return np.ascontiguousarray(entries)
+    out = np.zeros(len(entries), dtype=NEIGH_ENTRY_DTYPE)
+    for i, (ip, mac) in enumerate(entries):
+        out["ip"][i] = ip
+        out["mac"][i] = np.frombuffer(bytes(mac), dtype=np.uint8)
+    return out
+
+
+class NeighTable:
+    """The host-only neighbour table (gcl_neigh_tbl_*, include/gcl_host.h):
+    the table of Classifier.neigh_set / tx_hdr without a GPU."""
+
+    def __init__(self, hash_bits=None):
+        self._tbl = ctypes.c_void_p(lib.gcl_neigh_tbl_new())
+        if not self._tbl:
+            raise MemoryError("gcl_neigh_tbl_new")
+        if hash_bits is not None:
+            self.hash_bits(hash_bits)
+
+    def close(self):
+        if self._tbl:
+            lib.gcl_neigh_tbl_free(self._tbl)
+            self._tbl = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def hash_bits(self, bits):
+        """The test knob: only the low @bits of the internal hash, from the next set on."""
+        return _check(lib.gcl_neigh_tbl_hash_bits(self._tbl, bits), "gcl_neigh_tbl_hash_bits")
+
+    def set(self, entries):
+        e = neigh_entries(entries)
+        return _check(lib.gcl_neigh_tbl_set(self._tbl, e.ctypes.data if len(e) else None, len(e)),
+                      "gcl_neigh_tbl_set")
+
+    def __len__(self):
+        return lib.gcl_neigh_tbl_count(self._tbl)
+
+    def lookup(self, ip):
+        """The mac (six bytes) that answers for @ip, or None."""
+        mac = (ctypes.c_uint8 * 6)()
+        return bytes(mac) if _check(lib.gcl_neigh_tbl_lookup(self._tbl, ip, ctypes.byref(mac)),
+                                    "gcl_neigh_tbl_lookup") else None
+
+
+TXH_OUT_FIELDS = ("cmd", "payload", "pkt_len", "tx_olflags", "hash", "status")
+
+
+def txh_net(addr, netmask, gateway, mac, min_pkt_size=0, flags=0):
+    """struct gcl_txh_net: one runtime's netcfg (addresses in host order, @mac six bytes)."""
+    return GclTxhNet(addr=addr, netmask=netmask, gateway=gateway, mac=(ctypes.c_uint8 * 6)(*bytes(mac)),
+                     min_pkt_size=min_pkt_size, flags=flags)
+
+
+def _txh_structs(desc, frame_off, m, frames, frames_len, shm_base, cap, net, out, counts):
+    """The two structs of gcl_tx_hdr / gcl_tx_hdr_host, sizes checked; @out
+    maps TXH_OUT_FIELDS to buffers (hash may be None)."""
+    for arr, w in ((desc, 32), (frame_off, 8), (out["cmd"], 8), (out["payload"], 8), (out["pkt_len"], 2),
+                   (out["tx_olflags"], 1), (out["hash"], 4), (out["status"], 1)):
+        if arr is not None and _nbytes(arr) < w * m:
+            raise ValueError("per-entry array too small")
+    if counts is not None and _nbytes(counts) < 8 * TXHC_NR:
+        raise ValueError("counts buffer too small")
+    tin = GclTxhIn(size=ctypes.sizeof(GclTxhIn), desc=_ptr(desc), frame_off=_ptr(frame_off), m=m,
+                   frames=_ptr(frames), frames_len=_frames_len(frames, frames_len), shm_base=shm_base,
+                   cap=cap, net=net)
+    tout = GclTxhOut(**{f: _ptr(out[f]) for f in TXH_OUT_FIELDS})
+    return tin, tout
+
+
+def tx_hdr_host(desc, frame_off, frames, net, table=None, rss_key=None, m=None, frames_len=None,
+                shm_base=0, cap=0, out=None, counts=None):
+    """gcl_tx_hdr_host: the rule of Classifier.tx_hdr on the CPU over numpy
+    arrays.  @desc is TXH_DESC_DTYPE[m], @frame_off u64[m], @frames a writable
+    uint8 array, @net a txh_net(), @table a NeighTable (None: empty), @rss_key
+    the 40-byte Toeplitz key (None: CALADAN_RSS_KEY).  @out maps
+    TXH_OUT_FIELDS to arrays (u64, u64, u16, u8, u32, u8); the ones left out
+    are allocated; hash=None in @out leaves it out.  @counts is a
+    u64[TXHC_NR], accumulated.  Returns the dict."""
+    m = len(desc) if m is None else m
+    out = dict(out or {})
+    for f, dt in (("cmd", np.uint64), ("payload", np.uint64), ("pkt_len", np.uint16),
+                  ("tx_olflags", np.uint8), ("hash", np.uint32), ("status", np.uint8)):
+        if f not in out:
+            out[f] = np.zeros(max(m, 1), dtype=dt)
+    tin, tout = _txh_structs(desc, frame_off, m, frames, frames_len, shm_base, cap, net, out, counts)
+    key = CALADAN_RSS_KEY if rss_key is None else bytes(rss_key)
+    if len(key) != 40:
+        raise ValueError("rss_key: 40 bytes")
+    _check(lib.gcl_tx_hdr_host(table._tbl if table is not None else None, key, ctypes.byref(tin),
+                               ctypes.byref(tout), _ptr(counts)), "gcl_tx_hdr_host")
+    return out
 
 
 def runtime_ip(r: int) -> int:
@@ -1167,6 +1314,37 @@ class Classifier:
         _check(lib.gcl_sock_lookup(self._ctx, ctypes.byref(b), _ptr(verdicts), _ptr(sock), _ptr(counts),
                                    stream), "gcl_sock_lookup")
         return sock
+
+    def neigh_set(self, entries):
+        """gcl_neigh_set: replace the context's neighbour table (neigh_entries
+        says what @entries may be; an empty sequence clears it)."""
+        e = neigh_entries(entries)
+        return _check(lib.gcl_neigh_set(self._ctx, e.ctypes.data if len(e) else None, len(e)),
+                      "gcl_neigh_set")
+
+    def tx_hdr(self, desc, frame_off, m, frames, net, frames_len=None, shm_base=0, cap=0, out=None,
+               counts=None, stream=None):
+        """gcl_tx_hdr: the Ethernet, IPv4 and UDP or TCP headers, the next hop
+        and the txpkt command of @m segments of one runtime on the GPU,
+        asynchronous.  @desc is a device uint8[m, 32] holding TXH_DESC_DTYPE
+        records (16-B aligned), @frame_off a device int64[m], @frames the
+        device tx region, @net a txh_net().  @out maps TXH_OUT_FIELDS to
+        device buffers; the ones left out are allocated on @frames' device
+        (cmd and payload int64, pkt_len int16, tx_olflags and status uint8,
+        hash int32); hash=None in @out leaves it out.  @counts is a device
+        u64[TXHC_NR], accumulated.  Returns the dict: frame_off, pkt_len,
+        tx_olflags and hash are l4_csum's and copy_batch's inputs."""
+        import torch
+        dev = frames.device if hasattr(frames, "device") else None
+        out = dict(out or {})
+        for f, dt in (("cmd", torch.int64), ("payload", torch.int64), ("pkt_len", torch.int16),
+                      ("tx_olflags", torch.uint8), ("hash", torch.int32), ("status", torch.uint8)):
+            if f not in out:
+                out[f] = torch.empty(max(m, 1), dtype=dt, device=dev)
+        tin, tout = _txh_structs(desc, frame_off, m, frames, frames_len, shm_base, cap, net, out, counts)
+        _check(lib.gcl_tx_hdr(self._ctx, ctypes.byref(tin), ctypes.byref(tout), _ptr(counts), stream),
+               "gcl_tx_hdr")
+        return out
 
     def copy_batch(self, src, src_off, length, n, dst, dst_off=None, dst_stride=0, tx_olflags=None,
                    hash=None, src_len=None, dst_len=None, dst_cap=0, len_hint=0, group=0,

@@ -177,6 +177,44 @@ int gcl_sock_tbl_lookup_host(const struct gcl_sock_tbl *tbl, uint8_t vbytes, uin
                              uint32_t *sock, uint64_t *counts);
 
 /*
+ * The neighbour table of gcl_neigh_set / gcl_tx_hdr (gclassify.h) as a
+ * host-only object: the same entry checks, the same table image and the same
+ * probe (one shared inline function), with no GPU.  A context embeds one.
+ *
+ * gcl_neigh_tbl_new    - an empty table, or NULL (no memory).
+ * gcl_neigh_tbl_set    - gcl_neigh_set: replace the whole set; the same
+ *                        errors, the previous set kept on any of them.
+ * gcl_neigh_tbl_hash_bits - a test knob: use only the low @bits (1..32) of the
+ *                        table's internal hash from the next gcl_neigh_tbl_set
+ *                        on, so that both buckets of many addresses collide:
+ *                        the longest kick chains, and the placement failure
+ *                        (-ENOSPC).  32 is the production value.  0 or -EINVAL.
+ * gcl_neigh_tbl_count  - entries in the table.
+ * gcl_neigh_tbl_lookup - 1 and @mac filled when @ip is in the table, 0 when it
+ *                        is not, -EINVAL for a NULL tbl or mac.
+ *
+ * gcl_tx_hdr_host - the rule of gcl_tx_hdr (gclassify.h) on the CPU over host
+ * pointers, for the segments the GPU did not see: sequential plain C with the
+ * per-entry rule the kernel shares.  @tbl is the neighbour table (NULL: an
+ * empty one), @rss_key the 40-byte key a context would have in cfg.rss_key;
+ * @in and @out are gcl_tx_hdr's structs with every pointer a host pointer, and
+ * any byte alignment of the arrays is accepted; @counts is a host
+ * u64[GCL_TXHC_NR], ACCUMULATED, may be NULL.  The same outputs, the same
+ * bytes written and the same guarantee.  0, or -EINVAL for a NULL rss_key and
+ * for what gcl_tx_hdr refuses (the ctx and the alignments apart).  m == 0 is a
+ * no-op.
+ */
+struct gcl_neigh_tbl;
+struct gcl_neigh_tbl *gcl_neigh_tbl_new(void);
+void gcl_neigh_tbl_free(struct gcl_neigh_tbl *tbl);
+int gcl_neigh_tbl_set(struct gcl_neigh_tbl *tbl, const struct gcl_neigh_entry *e, uint32_t n);
+int gcl_neigh_tbl_hash_bits(struct gcl_neigh_tbl *tbl, uint32_t bits);
+uint32_t gcl_neigh_tbl_count(const struct gcl_neigh_tbl *tbl);
+int gcl_neigh_tbl_lookup(const struct gcl_neigh_tbl *tbl, uint32_t ip, uint8_t mac[6]);
+int gcl_tx_hdr_host(const struct gcl_neigh_tbl *tbl, const uint8_t rss_key[40],
+                    const struct gcl_txh_in *in, const struct gcl_txh_out *out, uint64_t *counts);
+
+/*
  * gcl_host_deliver - consume @n verdicts in order.
  * @clients_by_id  dp.clients_by_id (iokernel/defs.h:386), @max_runtimes long
  * @clients        dp.clients[0..nr_clients) (broadcast order, rx.c:175)

@@ -1352,6 +1352,149 @@ int gcl_l4_payload(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct 
                    const struct gcl_pay_out *out, uint64_t *counts,
                    void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/*
+ * Transmit headers: what the runtime does to a segment between its socket and
+ * its txpkt queue, for a batch whose payloads already sit in the tx region
+ * behind their headroom.  udp_send_raw (runtime/net/udp.c:24-40) or
+ * __tcp_add_tcphdr (runtime/net/tcp_out.c:54-81) writes the L4 header,
+ * net_tx_ip (runtime/net/core.c:686-737) the IPv4 header, the route, the ARP
+ * hit (arp_lookup's hot path, runtime/net/arp.c:331-344), the loopback hint
+ * and through net_tx_eth (core.c:581-590) the Ethernet header, and
+ * net_tx_iokernel (core.c:504-538) the padding, the txpkt_xmit_cmd and its
+ * payload word.  gcl_tx_hdr does all of that for m segments of one runtime on
+ * the GPU.  The transmit chain on one stream:
+ *
+ *   gcl_copy_batch (payloads to their place behind the headroom)
+ *   -> gcl_tx_hdr -> gcl_l4_csum GCL_L4_FILL (offs = frame_off, pkt_len and
+ *   tx_olflags as written here) -> the NIC, or gcl_copy_batch (src_off =
+ *   frame_off, len = pkt_len, tx_olflags, hash) + gcl_classify for frames to
+ *   a runtime on the same machine.
+ *
+ * The neighbour table is a context's ARP cache.  gcl_neigh_set replaces the
+ * whole set (n == 0 clears it); an entry stands for an arp_entry whose state
+ * is not ARP_STATE_PROBING: only resolved addresses are given.  -EINVAL for a
+ * NULL ctx, or a NULL @e with n > 0; -EEXIST when two entries share their ip;
+ * -ENOSPC for more than GCL_NEIGH_MAX_ENTRIES or when the placement failed;
+ * -ENOMEM.  On any error the previous set stays in place.  A change reaches
+ * the device on the stream of the next gcl_tx_hdr, before its kernel (the
+ * snapshot semantics of gcl_sock_set); the classify and socket tables and
+ * their uploads are not touched.  It works on every context, whatever its
+ * verdict width.
+ *
+ * Entry j, with o = frame_off[j], hl = 8 for UDP and 4 * tcp_off for TCP,
+ * tot = 20 + hl + paylen, len = 14 + tot and elen = max(len,
+ * net.min_pkt_size); the first status that matches decides:
+ *
+ *   GCL_TXH_REFUSED when proto is not 6 or 17, when the segment is TCP and
+ *     tcp_off is outside 5..15, when len > 65535, when cap != 0 and
+ *     elen > cap, or when o > frames_len or elen > frames_len - o (no sum is
+ *     formed, so any o is judged rightly).  No frame byte is written; cmd =
+ *     payload = 0, pkt_len = 0, tx_olflags = 0, hash = 0.
+ *   Otherwise the L4 and IP headers are written.  saddr = lip, or when lip is
+ *     0: 127.0.0.1 if rip is 127.0.0.1, else net.addr (core.c:693-698).
+ *     UDP, bytes 34-41: sport, dport, hton16(paylen + 8), checksum 0.
+ *     TCP, bytes 34-53: sport, dport, seq, ack, off << 4, flags, win, the
+ *     non-complemented ipv4_phdr_cksum(6, saddr, rip, hl + paylen) as
+ *     inc/net/chksum.h:110-126 stores it (the value the runtime leaves for
+ *     the NIC, and the one FILL overwrites), urgent 0.  Bytes [54, 34 + hl),
+ *     the options, are the caller's and are NOT written.
+ *     IPv4, bytes 14-33: 0x45, tos = has_ecn ? ecn & 3 : 0, hton16(tot),
+ *     id 0, hton16(IP_DF), ttl 64, the protocol, checksum 0 (ipv4_cksum with
+ *     GCL_TXH_IP_CSUM), saddr, daddr = rip.
+ *   GCL_TXH_SELF when rip == net.addr or rip is 127.0.0.1
+ *     (net_tx_local_loopback, core.c:705-706: the runtime handles the segment
+ *     itself).  The Ethernet header is not written; cmd = payload = 0,
+ *     pkt_len = len, tx_olflags = 0, hash = 0.
+ *   Otherwise nh = rip when (rip & netmask) == (addr & netmask), else gateway,
+ *     and nh is looked up in the neighbour table.
+ *   GCL_TXH_NONEIGH on a miss (the -EINPROGRESS path: the host's ARP code
+ *     takes the frame).  The Ethernet header is not written; cmd = payload =
+ *     0, pkt_len = len, hash = 0, tx_olflags = IP_CHKSUM | IPV4 | (TCP ?
+ *     TCP_CHKSUM : 0) (core.c:709 sets them before the lookup).
+ *   GCL_TXH_OK on a hit.  Bytes 0-13: dhost = the entry's mac, shost =
+ *     net.mac, type 0x0800.  local = (mac == net.mac) (is_local, arp.c:62-65);
+ *     tx_olflags is the flags above plus TXFLAG_LOCAL | TXFLAG_LOCAL_HINT when
+ *     local.  When local, hash = do_toeplitz(net.addr, nh, lport, rport) with
+ *     the context's cfg.rss_key (net.addr, not saddr, as core.c:730) and
+ *     dst_ip = nh; else hash = 0 and dst_ip = 0.  When len < min_pkt_size,
+ *     bytes [len, min_pkt_size) become 0 and pkt_len = min_pkt_size
+ *     (core.c:513-517); else pkt_len = len.  cmd = dst_ip | (u64)pkt_len << 32
+ *     | (u64)tx_olflags << 48 (txcmd is TXPKT_NET_XMIT = 0: the top bit is
+ *     clear); payload = (shm_base + o) | (u64)(hash & 0xFFFF) << 48.
+ *
+ * @counts is a device u64[GCL_TXHC_NR], ACCUMULATED, may be NULL: OK, SELF,
+ * NONEIGH, REFUSED, LOCAL (the OK entries that got the hint) and BYTES
+ * (pkt_len of the OK entries); per call the first four sum to m.
+ *
+ * Guarantee: no content of desc, frame_off or the table causes a read outside
+ * the m-element arrays or the table image, or a write outside the m-element
+ * outputs, counts and the bytes named above, which lie inside [o, o + elen) of
+ * a frame that was not refused.  The TCP option bytes, the payload behind the
+ * header and every byte outside the frame are not written, not even with the
+ * value they already had: neighbouring frames belong to other lanes, so each
+ * store has the width of what it writes or less and no wider word is
+ * read-modify-written (gcl_copy_batch's discipline).  Frames that overlap are
+ * the caller's error; nothing is written out of bounds even so.
+ *
+ * Asynchronous on @hip_stream; no allocation and no host synchronisation
+ * beyond the table upload after a change.  m == 0 is a no-op.  -EINVAL for a
+ * NULL ctx, in, out, desc, frame_off, frames, cmd, payload, pkt_len,
+ * tx_olflags or status; a wrong in->size; m > 2^31; frames_len == UINT64_MAX;
+ * an array that is not aligned to its element (desc: 16 B).  -EIO when the
+ * launch fails; -ENOMEM or -EIO when the table upload fails.
+ */
+#define GCL_NEIGH_MAX_ENTRIES (1u << 16)
+struct gcl_neigh_entry { uint32_t ip; uint8_t mac[6]; uint16_t pad; };  /* ip in host order */
+int gcl_neigh_set(struct gcl_ctx *ctx, const struct gcl_neigh_entry *e, uint32_t n);
+
+/* status[j] and the first four counter slots */
+#define GCL_TXH_OK       0
+#define GCL_TXH_SELF     1
+#define GCL_TXH_NONEIGH  2
+#define GCL_TXH_REFUSED  3
+enum { GCL_TXHC_OK = 0, GCL_TXHC_SELF, GCL_TXHC_NONEIGH, GCL_TXHC_REFUSED, GCL_TXHC_LOCAL,
+       GCL_TXHC_BYTES, GCL_TXHC_NR = 8 };
+#define GCL_TXH_IP_CSUM  0x01    /* gcl_txh_net.flags */
+struct gcl_txh_desc {          /* 32 B, 16-B aligned, host order: what the runtime knows of a segment */
+	uint32_t lip, rip;         /* laddr.ip (0: see above), raddr.ip */
+	uint16_t lport, rport;
+	uint8_t  proto;            /* 6 or 17 */
+	uint8_t  tcp_flags;        /* TCP byte 13; ignored for UDP */
+	uint8_t  tcp_off;          /* TCP data offset in words, 5..15; ignored for UDP */
+	uint8_t  ecn;              /* bit 7: has_ecn; bits 0-1: the ECN codepoint (core.c:602-606) */
+	uint32_t seq, ack;         /* TCP; ignored for UDP */
+	uint16_t win;              /* TCP window as it goes on the wire (already scaled) */
+	uint16_t paylen;           /* bytes behind the L4 header (UDP: behind its 8 B; TCP: behind 4 * tcp_off) */
+	uint32_t pad;
+};
+struct gcl_txh_net {           /* one runtime's netcfg */
+	uint32_t addr, netmask, gateway;   /* host order */
+	uint8_t  mac[6];
+	uint8_t  min_pkt_size;     /* netcfg.min_pkt_size, 0 = none */
+	uint8_t  flags;            /* GCL_TXH_IP_CSUM: write ipv4_cksum into the header (netcfg.no_tx_offloads) */
+};
+struct gcl_txh_in {
+	uint32_t size, pad;                /* sizeof(struct gcl_txh_in) */
+	const struct gcl_txh_desc *desc;   /* device [m] */
+	const uint64_t *frame_off;         /* device u64[m]: where each frame's Ethernet header starts in @frames, any byte alignment */
+	uint64_t m;                        /* <= 2^31 */
+	uint8_t *frames; uint64_t frames_len;   /* the tx region (device) */
+	uint64_t shm_base;                 /* payload[j] = shm_base + frame_off[j] | hash16 << 48 */
+	uint32_t cap;                      /* a frame longer than this is refused; 0 = no cap of its own */
+	uint32_t pad2;
+	struct gcl_txh_net net;
+};
+struct gcl_txh_out {                   /* device, m entries each, aligned to their element */
+	uint64_t *cmd;       /* required: txpkt_xmit_cmd.lrpc_cmd (inc/iokernel/queue.h:82-93) */
+	uint64_t *payload;   /* required: txpkt_to_payload(shmptr, (uint16_t)hash) (queue.h:120-124) */
+	uint16_t *pkt_len;   /* required: cmd.len; with frame_off it is gcl_batch.offs/pkt_len of FILL and src_off/len of gcl_copy_batch */
+	uint8_t  *tx_olflags;/* required: cmd.olflags, the tx_olflags of gcl_l4_in and gcl_copy_in */
+	uint32_t *hash;      /* optional: m->hash (gcl_copy_in.hash) */
+	uint8_t  *status;    /* required */
+};
+int gcl_tx_hdr(struct gcl_ctx *ctx, const struct gcl_txh_in *in, const struct gcl_txh_out *out,
+               uint64_t *counts, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
