@@ -9,6 +9,7 @@
 #include "../../include/gcl_host.h"
 #include "../../include/gclassify.h"
 #include "gcl_pay.h"
+#include "gcl_seg.h"
 #include "gcl_txh.h"
 
 #define ROT(x, k) (((x) << (k)) | ((x) >> (32 - (k))))
@@ -493,6 +494,77 @@ int gcl_tx_hdr_host(const struct gcl_neigh_tbl *tbl, const uint8_t rss_key[40],
 	}
 	if (counts)
 		for (int k = 0; k < GCL_TXHC_NR; k++)
+			counts[k] += c[k];
+	return 0;
+}
+
+/* The rule of gcl_tx_seg (gclassify.h) on the CPU: gcl_seg_rule of gcl_seg.h
+ * for every write in turn, the two sums running, gcl_seg_emit for every
+ * segment of a write that fits. */
+int gcl_tx_seg_host(const struct gcl_seg_in *in, const struct gcl_seg_out *out, uint64_t *counts)
+{
+	uint64_t c[GCL_SEGC_NR] = {0}, S = 0, B = 0, segs = 0, bytes = 0;
+
+	if (!in || !out || in->size != sizeof(*in) || in->m > (1ull << 31) || in->seg_cap > (1ull << 31) ||
+	    in->stride > GCL_SEG_MAX_STRIDE || in->lead > GCL_SEG_MAX_LEAD || in->udp_max > GCL_SEG_MAX_UDP ||
+	    in->blocks > GCL_SEG_MAX_BLOCKS || !out->total_segs || !out->total_bytes)
+		return -EINVAL;
+	if (in->m && (!in->send || !out->status || !out->sent || !out->snd_nxt_out || !out->seg_first ||
+	              !out->nseg))
+		return -EINVAL;
+	if (in->m && in->seg_cap && (!out->desc || !out->frame_off || !out->src_off || !out->len ||
+	                             !out->dst_off))
+		return -EINVAL;
+	if (((uintptr_t)in->send & 15) || ((uintptr_t)out->sent & 3) || ((uintptr_t)out->snd_nxt_out & 3) ||
+	    ((uintptr_t)out->seg_first & 3) || ((uintptr_t)out->nseg & 3) || ((uintptr_t)out->desc & 15) ||
+	    ((uintptr_t)out->frame_off & 7) || ((uintptr_t)out->src_off & 7) || ((uintptr_t)out->len & 1) ||
+	    ((uintptr_t)out->dst_off & 7) || ((uintptr_t)out->send_idx & 3) || ((uintptr_t)out->total_segs & 7) ||
+	    ((uintptr_t)out->total_bytes & 7) || ((uintptr_t)counts & 7))
+		return -EINVAL;
+	const uint64_t bcap = gcl_seg_byte_cap(in->frames_len, in->frame_base, in->stride, in->lead);
+
+	for (uint64_t i = 0; i < in->m; i++) {
+		uint32_t s[12];
+
+		memcpy(s, &in->send[i], sizeof(s)); /* little-endian host */
+		const struct gcl_seg_plan p = gcl_seg_rule(s, in->udp_max, in->stride, in->lead);
+		uint32_t status = p.status;
+		if (status == GCL_SEG_OK && (S + p.nseg > in->seg_cap || gcl_seg_sat(B, p.wbytes) > bcap))
+			status = GCL_SEG_NOSPACE;
+		const int ok = status == GCL_SEG_OK;
+
+		out->status[i] = (uint8_t)status;
+		out->sent[i] = ok ? p.L : 0;
+		out->snd_nxt_out[i] = s[4] + (ok ? p.L : 0);
+		out->seg_first[i] = (uint32_t)(S < in->seg_cap ? S : in->seg_cap);
+		out->nseg[i] = ok ? p.nseg : 0;
+		if (ok) {
+			const uint64_t first_byte = in->frame_base + in->lead + B;
+			for (uint32_t k = 0; k < p.nseg; k++) {
+				const struct gcl_seg_one r = gcl_seg_emit(s, k, first_byte, in->stride);
+				const uint64_t g = S + k;
+				memcpy(&out->desc[g], r.d, sizeof(out->desc[g]));
+				out->frame_off[g] = r.frame_off;
+				out->src_off[g] = r.src_off;
+				out->len[g] = (uint16_t)r.paylen;
+				out->dst_off[g] = r.dst_off;
+				if (out->send_idx)
+					out->send_idx[g] = (uint32_t)i;
+			}
+			segs += p.nseg;
+			bytes += p.wbytes;
+			c[GCL_SEGC_BYTES] += p.L;
+			c[GCL_SEGC_PUSH] += p.tcp;
+		}
+		c[status]++;
+		S += p.nseg;
+		B = gcl_seg_sat(B, p.wbytes);
+	}
+	c[GCL_SEGC_SEGS] = segs;
+	*out->total_segs = segs;
+	*out->total_bytes = bytes;
+	if (counts)
+		for (int k = 0; k < GCL_SEGC_NR; k++)
 			counts[k] += c[k];
 	return 0;
 }

@@ -91,6 +91,16 @@ TXH_DESC_DTYPE = np.dtype([("lip", "<u4"), ("rip", "<u4"), ("lport", "<u2"), ("r
                            ("seq", "<u4"), ("ack", "<u4"), ("win", "<u2"), ("paylen", "<u2"),
                            ("pad", "<u4")])
 NEIGH_ENTRY_DTYPE = np.dtype([("ip", "<u4"), ("mac", "u1", (6,)), ("pad", "<u2")])
+# gcl_tx_seg: the status byte, the counter slots, the cap on blocks, struct gcl_seg_send
+SEG_OK, SEG_REFUSED, SEG_NOSPACE = range(3)
+(SEGC_OK, SEGC_REFUSED, SEGC_NOSPACE, SEGC_SEGS, SEGC_BYTES, SEGC_PUSH) = range(6)
+SEGC_NR, SEG_MAX_BLOCKS = 8, 1024
+# its launches (csrc/gcl_seg.hip): writes or segments per tile
+SEG_TILE = 256
+SEG_SEND_DTYPE = np.dtype([("lip", "<u4"), ("rip", "<u4"), ("lport", "<u2"), ("rport", "<u2"),
+                           ("proto", "u1"), ("ecn", "u1"), ("mss", "<u2"), ("snd_nxt", "<u4"),
+                           ("ack", "<u4"), ("win", "<u2"), ("pad", "<u2"), ("len", "<u4"),
+                           ("winlen", "<u4"), ("pad2", "<u4"), ("src_off", "<u8")])
 STAT_NAMES = ["RX_UNREGISTERED_MAC", "RX_UNICAST_FAIL", "RX_BROADCAST_FAIL",
               "RX_FLOW_TAG_MATCH", "RX_UNHANDLED", "RX_HASH_MISSING", "RX_PULLED"]
 
@@ -313,6 +323,23 @@ class GclTxhOut(ctypes.Structure):
                 ("tx_olflags", ctypes.c_void_p), ("hash", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
+class GclSegIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("send", ctypes.c_void_p),
+                ("m", ctypes.c_uint64), ("seg_cap", ctypes.c_uint64), ("frame_base", ctypes.c_uint64),
+                ("frames_len", ctypes.c_uint64), ("stride", ctypes.c_uint32), ("lead", ctypes.c_uint32),
+                ("udp_max", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+SEG_WRITE_FIELDS = ("status", "sent", "snd_nxt_out", "seg_first", "nseg")
+SEG_SEG_FIELDS = ("desc", "frame_off", "src_off", "len", "dst_off", "send_idx")
+SEG_OUT_FIELDS = SEG_WRITE_FIELDS + SEG_SEG_FIELDS + ("total_segs", "total_bytes")
+
+
+class GclSegOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in SEG_OUT_FIELDS]
+
+
+assert ctypes.sizeof(GclSegIn) == 64 and ctypes.sizeof(GclSegOut) == 104 and SEG_SEND_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclTxhIn) == 88 and ctypes.sizeof(GclTxhNet) == 20 and TXH_DESC_DTYPE.itemsize == 32
 assert NEIGH_ENTRY_DTYPE.itemsize == 12
 assert ctypes.sizeof(GclPayIn) == 56 and ctypes.sizeof(GclPayOut) == 56 and PAY_META_DTYPE.itemsize == 16
@@ -408,6 +435,10 @@ def _load():
         "gcl_tx_hdr": (i32, [vp, ctypes.POINTER(GclTxhIn), ctypes.POINTER(GclTxhOut), vp, vp]),
         "gcl_tx_hdr_host": (i32, [vp, ctypes.c_char_p, ctypes.POINTER(GclTxhIn), ctypes.POINTER(GclTxhOut),
                                   vp]),
+        "gcl_tx_seg_workspace": (i32, [u64, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tx_seg": (i32, [vp, ctypes.POINTER(GclSegIn), ctypes.POINTER(GclSegOut), vp, vp,
+                             ctypes.c_size_t, vp]),
+        "gcl_tx_seg_host": (i32, [ctypes.POINTER(GclSegIn), ctypes.POINTER(GclSegOut), vp]),
         "gcl_neigh_tbl_new": (vp, []),
         "gcl_neigh_tbl_free": (None, [vp]),
         "gcl_neigh_tbl_set": (i32, [vp, vp, u32]),
@@ -835,6 +866,63 @@ def tx_hdr_host(desc, frame_off, frames, net, table=None, rss_key=None, m=None, 
     _check(lib.gcl_tx_hdr_host(table._tbl if table is not None else None, key, ctypes.byref(tin),
                                ctypes.byref(tout), _ptr(counts)), "gcl_tx_hdr_host")
     return out
+
+
+SEG_OUT_WIDTH = {"status": 1, "sent": 4, "snd_nxt_out": 4, "seg_first": 4, "nseg": 4, "desc": 32,
+                 "frame_off": 8, "src_off": 8, "len": 2, "dst_off": 8, "send_idx": 4}
+
+
+def _seg_structs(send, m, seg_cap, stride, lead, frame_base, frames_len, udp_max, blocks, out, counts):
+    """The two structs of gcl_tx_seg / gcl_tx_seg_host, sizes checked; @out
+    maps SEG_OUT_FIELDS to buffers (send_idx may be None)."""
+    if send is not None and _nbytes(send) < 48 * m:
+        raise ValueError("send array too small")
+    for f in SEG_WRITE_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < SEG_OUT_WIDTH[f] * m:
+            raise ValueError(f"{f}: per-write array too small")
+    for f in SEG_SEG_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < SEG_OUT_WIDTH[f] * seg_cap:
+            raise ValueError(f"{f}: per-segment array shorter than seg_cap")
+    for f in ("total_segs", "total_bytes"):
+        if out[f] is not None and _nbytes(out[f]) < 8:
+            raise ValueError(f"{f} too small")
+    if counts is not None and _nbytes(counts) < 8 * SEGC_NR:
+        raise ValueError("counts buffer too small")
+    sin = GclSegIn(size=ctypes.sizeof(GclSegIn), blocks=blocks, send=_ptr(send), m=m, seg_cap=seg_cap,
+                   frame_base=frame_base, frames_len=frames_len, stride=stride, lead=lead, udp_max=udp_max)
+    sout = GclSegOut(**{f: _ptr(out[f]) for f in SEG_OUT_FIELDS})
+    return sin, sout
+
+
+def tx_seg_host(send, seg_cap, stride=0, lead=0, frame_base=0, frames_len=0, udp_max=1472, m=None,
+                blocks=0, out=None, counts=None):
+    """gcl_tx_seg_host: the rule of Classifier.tx_seg on the CPU over numpy
+    arrays.  @send is SEG_SEND_DTYPE[m]; @out maps SEG_OUT_FIELDS to arrays
+    (per write u8, u32 x 4; per segment TXH_DESC_DTYPE, u64, u64, u16, u64,
+    u32, each @seg_cap long; the totals u64[1]); the ones left out are
+    allocated; send_idx=None in @out leaves it out.  @counts is a
+    u64[SEGC_NR], accumulated.  Returns the dict."""
+    m = len(send) if m is None else m
+    out = dict(out or {})
+    for f, dt, k in (("status", np.uint8, m), ("sent", np.uint32, m), ("snd_nxt_out", np.uint32, m),
+                     ("seg_first", np.uint32, m), ("nseg", np.uint32, m), ("desc", TXH_DESC_DTYPE, seg_cap),
+                     ("frame_off", np.uint64, seg_cap), ("src_off", np.uint64, seg_cap),
+                     ("len", np.uint16, seg_cap), ("dst_off", np.uint64, seg_cap),
+                     ("send_idx", np.uint32, seg_cap), ("total_segs", np.uint64, 1),
+                     ("total_bytes", np.uint64, 1)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    sin, sout = _seg_structs(send, m, seg_cap, stride, lead, frame_base, frames_len, udp_max, blocks, out,
+                             counts)
+    _check(lib.gcl_tx_seg_host(ctypes.byref(sin), ctypes.byref(sout), _ptr(counts)), "gcl_tx_seg_host")
+    return out
+
+
+def tx_seg_workspace(m, blocks=0):
+    """gcl_tx_seg_workspace: bytes of device scratch a call over @m writes takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tx_seg_workspace(m, blocks, ctypes.byref(need)), "gcl_tx_seg_workspace")
+    return need.value
 
 
 def runtime_ip(r: int) -> int:
@@ -1344,6 +1432,44 @@ class Classifier:
         tin, tout = _txh_structs(desc, frame_off, m, frames, frames_len, shm_base, cap, net, out, counts)
         _check(lib.gcl_tx_hdr(self._ctx, ctypes.byref(tin), ctypes.byref(tout), _ptr(counts), stream),
                "gcl_tx_hdr")
+        return out
+
+    def tx_seg(self, send, m, seg_cap, stride=0, lead=0, frame_base=0, frames_len=0, udp_max=1472,
+               blocks=0, out=None, counts=None, workspace=None, stream=None):
+        """gcl_tx_seg: cut @m socket writes of one runtime into tx segments on
+        the GPU, asynchronous.  @send is a device uint8[m, 48] holding
+        SEG_SEND_DTYPE records (16-B aligned).  @out maps SEG_OUT_FIELDS to
+        device buffers; the ones left out are allocated on @send's device
+        (status uint8, sent, snd_nxt_out, seg_first, nseg and send_idx int32,
+        desc uint8[seg_cap, 32], frame_off, src_off, dst_off and the totals
+        int64, len int16); send_idx=None in @out leaves it out.  @counts is a
+        device u64[SEGC_NR], accumulated.  The scratch is @workspace, or a
+        torch tensor kept on the classifier.  Returns the dict: src_off, len
+        and dst_off are copy_batch's src_off, length and dst_off, desc and
+        frame_off are tx_hdr's, and total_segs is their m."""
+        import torch
+        dev = send.device if hasattr(send, "device") else None
+        out = dict(out or {})
+        mm, cc = max(m, 1), max(seg_cap, 1)
+        for f, dt, shape in (("status", torch.uint8, (mm,)), ("sent", torch.int32, (mm,)),
+                             ("snd_nxt_out", torch.int32, (mm,)), ("seg_first", torch.int32, (mm,)),
+                             ("nseg", torch.int32, (mm,)), ("desc", torch.uint8, (cc, 32)),
+                             ("frame_off", torch.int64, (cc,)), ("src_off", torch.int64, (cc,)),
+                             ("len", torch.int16, (cc,)), ("dst_off", torch.int64, (cc,)),
+                             ("send_idx", torch.int32, (cc,)), ("total_segs", torch.int64, (1,)),
+                             ("total_bytes", torch.int64, (1,))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        sin, sout = _seg_structs(send, m, seg_cap, stride, lead, frame_base, frames_len, udp_max, blocks,
+                                 out, counts)
+        ws = workspace
+        if ws is None:
+            need = tx_seg_workspace(m, blocks)
+            ws = getattr(self, "_seg_ws", None)
+            if ws is None or ws.numel() < need or ws.device != out["total_segs"].device:
+                ws = self._seg_ws = torch.empty(need, dtype=torch.uint8, device=out["total_segs"].device)
+        _check(lib.gcl_tx_seg(self._ctx, ctypes.byref(sin), ctypes.byref(sout), _ptr(counts), _ptr(ws),
+                              _nbytes(ws), stream), "gcl_tx_seg")
         return out
 
     def copy_batch(self, src, src_off, length, n, dst, dst_off=None, dst_stride=0, tx_olflags=None,

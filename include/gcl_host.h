@@ -215,6 +215,21 @@ int gcl_tx_hdr_host(const struct gcl_neigh_tbl *tbl, const uint8_t rss_key[40],
                     const struct gcl_txh_in *in, const struct gcl_txh_out *out, uint64_t *counts);
 
 /*
+ * gcl_tx_seg_host - the rule of gcl_tx_seg (gclassify.h) on the CPU over host
+ * pointers, for the writes the GPU did not see: tcp_write3's window clamp and
+ * tcp_tx_send's segmenter loop (runtime/net/tcp.c:1362-1380, tcp_out.c:
+ * 313-386) and udp_write_to's size check (udp.c:590-591) in their closed form,
+ * sequential plain C with the per-write and per-segment rule the kernels
+ * share and no workspace.  @in and @out are gcl_tx_seg's structs with every
+ * pointer a host pointer (in->blocks is checked against GCL_SEG_MAX_BLOCKS and
+ * otherwise not looked at); @counts is a host u64[GCL_SEGC_NR], ACCUMULATED,
+ * may be NULL.  The same outputs, the same counts and the same guarantee.  0,
+ * or -EINVAL for what gcl_tx_seg refuses (the ctx and the workspace apart).
+ * m == 0 writes the two totals as 0 and nothing else.
+ */
+int gcl_tx_seg_host(const struct gcl_seg_in *in, const struct gcl_seg_out *out, uint64_t *counts);
+
+/*
  * gcl_host_deliver - consume @n verdicts in order.
  * @clients_by_id  dp.clients_by_id (iokernel/defs.h:386), @max_runtimes long
  * @clients        dp.clients[0..nr_clients) (broadcast order, rx.c:175)

@@ -1495,6 +1495,161 @@ struct gcl_txh_out {                   /* device, m entries each, aligned to the
 int gcl_tx_hdr(struct gcl_ctx *ctx, const struct gcl_txh_in *in, const struct gcl_txh_out *out,
                uint64_t *counts, void *hip_stream);
 
+/*
+ * Transmit segmentation: the first step of the transmit chain.  A runtime that
+ * writes to a socket cuts the bytes into segments on a core, one write at a
+ * time: tcp_write3 clamps the length to the send window (runtime/net/tcp.c:
+ * 1362-1380) and "the main TCP segmenter loop" of tcp_tx_send cuts it into
+ * mss-sized segments, the last one pushed (runtime/net/tcp_out.c:313-386);
+ * udp_write_to refuses a datagram above udp_get_payload_size() and sends one
+ * segment (runtime/net/udp.c:590-591).  gcl_tx_seg does that for m writes of
+ * one runtime on the GPU and writes, per segment and in send order, the inputs
+ * of the calls that follow:
+ *
+ *   gcl_tx_seg -> gcl_copy_batch (src = the writers' buffers; src_off, len and
+ *   dst_off as written here) -> gcl_tx_hdr (desc and frame_off as written
+ *   here) -> gcl_l4_csum GCL_L4_FILL -> the NIC or the loopback.
+ *
+ * It works on every context, whatever its verdict width, and touches no table.
+ *
+ * The rule for write i is the closed form of the reference's loop with
+ * push == true (tcp_write3 always passes it) and no tx_pending:
+ *   TCP (proto 6): L = min(len, winlen), nseg = max(1, ceil(L / mss)): the loop
+ *     is a do ... while, so L == 0 still sends one empty ACK|PSH segment and
+ *     the write returns 0.  Segment k has seq = snd_nxt + k * mss (mod 2^32),
+ *     paylen = min(mss, L - k * mss), tcp_off = 5, tcp_flags = ACK (0x10), plus
+ *     PSH (0x08) on the last segment; ack, win and ecn are the write's.
+ *   UDP (proto 17): L = len, nseg = 1, one datagram of L bytes (L == 0 is a
+ *     valid empty datagram); tcp_flags, tcp_off, seq, ack and win are 0.
+ *   GCL_SEG_REFUSED when proto is not 6 or 17; for TCP when mss == 0; for UDP
+ *     when len > udp_max (the runtime's -EMSGSIZE); and with slots (below) when
+ *     the write's largest frame does not fit one:
+ *     lead + 34 + hl + min(L, mss) > stride (UDP: L for min(L, mss); hl is 20
+ *     for TCP, 8 for UDP).  A refused write has no segments.
+ *
+ * The frame layout, both forms taken from one scan.  Every write that is not
+ * refused has a segment count n_i = nseg above and layout bytes w_i:
+ *   slots (stride != 0): w_i = n_i * stride, and
+ *     frame_off[g] = frame_base + g * stride + lead.
+ *   packed (stride == 0): frames go back to back, each padded to 16 B:
+ *     w_i = the sum of pad16(34 + hl + paylen) over the write's segments, and
+ *     segment k of write i lies at frame_base + lead + B_i +
+ *     k * pad16(34 + hl + mss) (all segments of a write but the last have the
+ *     same length).
+ * S_i and B_i are the sums of n and w over the writes before i that were not
+ * refused.  Write i, not refused, is GCL_SEG_NOSPACE when
+ *   S_i + n_i > seg_cap, or, when frames_len != 0, its frames would end past
+ *   it: B_i + w_i > frames_len - frame_base - (packed: lead), a test made
+ *   without forming a sum that can wrap (a frames_len below frame_base, or
+ *   below frame_base + lead when packed, leaves no room at all).
+ * Both sums count the NOSPACE writes too and only grow, so the NOSPACE writes
+ * are a suffix of the writes that were not refused: once one write does not
+ * fit, no later one is sent, as a runtime stops at a full queue.  A NOSPACE
+ * write writes no segment at all.  Otherwise the write is GCL_SEG_OK.
+ *
+ * Per-write outputs (m entries): status; sent = L and snd_nxt_out = snd_nxt + L
+ * (mod 2^32) for an OK write, sent = 0 and snd_nxt_out = snd_nxt otherwise
+ * (for UDP snd_nxt is just carried); nseg = the segments written for the write
+ * (n_i when OK, else 0); seg_first = min(S_i, seg_cap): where the write's
+ * segments start.  It never decreases with i, and for the OK writes it is
+ * exact.
+ * *total_segs = the sum of nseg[]: the m to give the three calls that follow.
+ * *total_bytes = the sum of w_i over the OK writes (slots: *total_segs *
+ * stride): the next frame would start at frame_base + *total_bytes (+ lead).
+ *
+ * Per-segment outputs, for g = seg_first[i] + k of an OK write i:
+ *   desc[g]     a full gcl_txh_desc: the write's tuple and ecn, the fields
+ *               above, paylen, pad 0.
+ *   frame_off[g] as the layout says (mod 2^64 when frames_len == 0 and the
+ *               caller's frame_base is absurd).
+ *   src_off[g]  = send.src_off + k * mss, a u64 sum mod 2^64 (gcl_copy_batch
+ *               reads an offset past its src_len as zeros).
+ *   len[g]      = paylen.
+ *   dst_off[g]  = frame_off[g] + 14 + 20 + hl.
+ *   send_idx[g] = i (optional: lets a completion find its write).
+ * Entries at and past *total_segs are not written, not even with the value
+ * they had.  gcl_tx_hdr refuses a frame above 65535 bytes: a TCP segment whose
+ * mss exceeds 65481 comes out of this call and is refused there.
+ *
+ * @counts is a device u64[GCL_SEGC_NR], ACCUMULATED, may be NULL: OK, REFUSED
+ * and NOSPACE writes (per call the three sum to m), SEGS (*total_segs), BYTES
+ * (the sum of sent[]) and PUSH (segments carrying PSH: one per OK TCP write).
+ *
+ * Guarantee: no content of the writes causes a read outside send[0, m) or the
+ * workspace, or a write outside the first min(*total_segs, seg_cap) entries of
+ * the per-segment arrays, the m-element per-write arrays, the two totals,
+ * counts and the workspace.
+ *
+ * Out of scope, and left with the runtime: push == false and tx_pending (the
+ * held tail of tcp_writev2's inner iovecs), retransmission, the SYN, FIN and
+ * RST segments, tx_exclusive and the wait queues.  Several writes of one
+ * connection may share a batch only when the caller gives each its own
+ * snd_nxt (and winlen): the call does not chain them.
+ *
+ * gcl_tx_seg_workspace - bytes of device scratch a call takes: 16 per write
+ *   plus 32 per contiguous range the writes are cut into (in->blocks of them,
+ *   or the cap GCL_SEG_MAX_BLOCKS when blocks is 0) plus 16.  -EINVAL for a
+ *   NULL @bytes, m > 2^31 or blocks > GCL_SEG_MAX_BLOCKS.
+ * gcl_tx_seg - asynchronous on @hip_stream: four launches ordered by the
+ *   stream alone; no block waits for another.  No allocation, no host
+ *   synchronisation.  @workspace (device, 16-B aligned) need not be zeroed and
+ *   may be reused by the next call on the same stream.  m == 0 writes the two
+ *   totals as 0 and nothing else.  -EINVAL for a NULL ctx, in or out; a wrong
+ *   in->size; m or seg_cap > 2^31; stride > 2^20; lead > 65535; udp_max >
+ *   65507; blocks > GCL_SEG_MAX_BLOCKS; a NULL total_segs or total_bytes; with
+ *   m > 0 a NULL send, status, sent, snd_nxt_out, seg_first or nseg; with m > 0
+ *   and seg_cap > 0 a NULL desc, frame_off, src_off, len or dst_off; any given
+ *   array that is not aligned to its element (send and desc: 16 B); a NULL
+ *   workspace, one that is not 16-B aligned or one smaller than
+ *   gcl_tx_seg_workspace says.  -EIO when a launch fails.
+ */
+/* status[i] and the first three counter slots */
+#define GCL_SEG_OK       0
+#define GCL_SEG_REFUSED  1
+#define GCL_SEG_NOSPACE  2
+#define GCL_SEG_MAX_BLOCKS 1024  /* the cap on in->blocks */
+enum { GCL_SEGC_OK = 0, GCL_SEGC_REFUSED, GCL_SEGC_NOSPACE, GCL_SEGC_SEGS, GCL_SEGC_BYTES,
+       GCL_SEGC_PUSH, GCL_SEGC_NR = 8 };
+struct gcl_seg_send {          /* 48 B, 16-B aligned, host order: one socket write */
+	uint32_t lip, rip;         /* as in gcl_txh_desc */
+	uint16_t lport, rport;
+	uint8_t  proto;            /* 6 or 17 */
+	uint8_t  ecn;              /* as in gcl_txh_desc */
+	uint16_t mss;              /* TCP: pcb.snd_mss */
+	uint32_t snd_nxt, ack;     /* TCP: pcb.snd_nxt, tx_last_ack */
+	uint16_t win, pad;         /* TCP: the window as __tcp_add_tcphdr would write it */
+	uint32_t len;              /* the write's length */
+	uint32_t winlen;           /* TCP: snd_una + snd_wnd - snd_nxt; ignored for UDP */
+	uint32_t pad2;
+	uint64_t src_off;          /* where the write's bytes start in the source region of the later gcl_copy_batch */
+};
+struct gcl_seg_in {
+	uint32_t size, blocks;             /* sizeof(struct gcl_seg_in); blocks: 0 = the library's choice, else
+	                                      the number of contiguous ranges the scan is cut into (tests) */
+	const struct gcl_seg_send *send;   /* device [m] */
+	uint64_t m;                        /* <= 2^31 */
+	uint64_t seg_cap;                  /* <= 2^31: the length of every per-segment output array */
+	uint64_t frame_base;               /* where the layout starts in the tx region */
+	uint64_t frames_len;               /* the tx region's length; 0: no limit */
+	uint32_t stride;                   /* != 0: slots of this many bytes; 0: packed */
+	uint32_t lead;                     /* bytes in front of every frame (slots) or of the first (packed) */
+	uint32_t udp_max;                  /* udp_get_payload_size() */
+	uint32_t pad;
+};
+struct gcl_seg_out {                   /* device, aligned to their element */
+	uint8_t  *status;                  /* [m] */
+	uint32_t *sent, *snd_nxt_out, *seg_first, *nseg;   /* [m] */
+	struct gcl_txh_desc *desc;         /* [seg_cap], 16-B aligned */
+	uint64_t *frame_off, *src_off;     /* [seg_cap] */
+	uint16_t *len;                     /* [seg_cap] */
+	uint64_t *dst_off;                 /* [seg_cap] */
+	uint32_t *send_idx;                /* [seg_cap], optional */
+	uint64_t *total_segs, *total_bytes;/* u64[1] each, required */
+};
+int gcl_tx_seg_workspace(uint64_t m, uint32_t blocks, size_t *bytes);
+int gcl_tx_seg(struct gcl_ctx *ctx, const struct gcl_seg_in *in, const struct gcl_seg_out *out,
+               uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
