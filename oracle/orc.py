@@ -17,6 +17,7 @@ REF_CRC = os.path.join(HERE, "_ref", "libcrc_ref.so")
 REF_HOST = os.path.join(HERE, "_ref", "libhost_ref.so")
 REF_CORE = os.path.join(HERE, "_ref", "libcore_ref.so")
 REF_TRANS = os.path.join(HERE, "_ref", "libtrans_ref.so")
+REF_TCPOUT = os.path.join(HERE, "_ref", "libtcpout_ref.so")
 TRANS_DTYPE = np.dtype([("h5", "<u4"), ("h3", "<u4")])
 
 NR_STATS = 8
@@ -160,6 +161,95 @@ def ref_trans():
         f(seed, proto, lip, lport, rip, rport, ctypes.byref(out))
         return out[0], out[1]
     return call
+
+
+def ref_tcpout():
+    """The reference's own tcp_push_tcphdr (runtime/net/tcp_out.c:54-87) and
+    inc/net/chksum.h routines (oracle/_ref/libtcpout_ref.so, exported by
+    oracle/ref_tcpout.c), or None.  The object has
+      tcphdr(no_tx_offloads, lip, lport, rip, rport, seq, ack, win, wscale,
+             flags, off, payload) -> the 20 header bytes,
+      raw_cksum(buf), ipv4_phdr_cksum(proto, saddr, daddr, l4len),
+      ipv4_udptcp_cksum(proto, saddr, daddr, l4 bytes), ipv4_cksum(20 bytes)
+    -> the uint16_t the routine returns (the reference stores it as it is:
+    its two bytes in memory are value & 0xFF, value >> 8)."""
+    if not os.path.exists(REF_TCPOUT):
+        return None
+    l = ctypes.CDLL(REF_TCPOUT)
+    u8, u16, u32 = ctypes.c_uint8, ctypes.c_uint16, ctypes.c_uint32
+    l.ref_tcp_push_tcphdr.restype = ctypes.c_int
+    l.ref_tcp_push_tcphdr.argtypes = [ctypes.c_int, u32, u16, u32, u16, u32, u32, u32, u32, u8, u8, u16,
+                                      ctypes.c_char_p, ctypes.POINTER(u8 * 20)]
+    l.ref_raw_cksum.restype = u16
+    l.ref_raw_cksum.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+    l.ref_ipv4_phdr_cksum.restype = u16
+    l.ref_ipv4_phdr_cksum.argtypes = [u8, u32, u32, u16]
+    l.ref_ipv4_udptcp_cksum.restype = u16
+    l.ref_ipv4_udptcp_cksum.argtypes = [u8, u32, u32, u16, ctypes.c_char_p]
+    l.ref_ipv4_cksum.restype = u16
+    l.ref_ipv4_cksum.argtypes = [ctypes.c_char_p]
+
+    class Ref:
+        @staticmethod
+        def tcphdr(no_tx_offloads, lip, lport, rip, rport, seq, ack, win, wscale, flags, off, payload):
+            out = (u8 * 20)()
+            payload = bytes(payload)
+            ret = l.ref_tcp_push_tcphdr(no_tx_offloads, lip, lport, rip, rport, seq, ack, win, wscale,
+                                        flags, off, len(payload), payload, ctypes.byref(out))
+            if ret:
+                raise ValueError(f"ref_tcp_push_tcphdr: {ret}")
+            return bytes(out)
+
+        @staticmethod
+        def raw_cksum(buf):
+            buf = bytes(buf)
+            return l.ref_raw_cksum(buf, len(buf))
+
+        @staticmethod
+        def ipv4_phdr_cksum(proto, saddr, daddr, l4len):
+            return l.ref_ipv4_phdr_cksum(proto, saddr, daddr, l4len)
+
+        @staticmethod
+        def ipv4_udptcp_cksum(proto, saddr, daddr, l4):
+            l4 = bytes(l4)
+            return l.ref_ipv4_udptcp_cksum(proto, saddr, daddr, len(l4), l4)
+
+        @staticmethod
+        def ipv4_cksum(hdr):
+            hdr = bytes(hdr)
+            if len(hdr) != 20:
+                raise ValueError("ipv4_cksum: 20 bytes")
+            return l.ref_ipv4_cksum(hdr)
+    return Ref
+
+
+def ref_txip():
+    """The reference's own net_push_iphdr and net_get_ip_route
+    (runtime/net/core.c:592-626, oracle/_ref/libcore_ref.so), or None, as
+    (iphdr, route): iphdr(no_tx_offloads, proto, daddr, saddr, l4bytes,
+    aux=None or (has_ecn, ecn)) -> the 20 header bytes; route(addr, netmask,
+    gateway, daddr) -> the next hop."""
+    if not os.path.exists(REF_CORE):
+        return None
+    l = ctypes.CDLL(REF_CORE)
+    if not hasattr(l, "ref_net_push_iphdr"):
+        return None
+    u8, u32 = ctypes.c_uint8, ctypes.c_uint32
+    l.ref_net_push_iphdr.restype = ctypes.c_int
+    l.ref_net_push_iphdr.argtypes = [ctypes.c_int, u8, u32, u32, ctypes.c_uint16, ctypes.c_int,
+                                     ctypes.c_int, u8, ctypes.POINTER(u8 * 20)]
+    l.ref_net_get_ip_route.restype = u32
+    l.ref_net_get_ip_route.argtypes = [u32, u32, u32, u32]
+
+    def iphdr(no_tx_offloads, proto, daddr, saddr, l4bytes, aux=None):
+        out = (u8 * 20)()
+        has_ecn, ecn = aux if aux is not None else (0, 0)
+        ret = l.ref_net_push_iphdr(no_tx_offloads, proto, daddr, saddr, l4bytes, aux is not None,
+                                   has_ecn, ecn, ctypes.byref(out))
+        if ret:
+            raise ValueError(f"ref_net_push_iphdr: {ret}")
+        return bytes(out)
+    return iphdr, l.ref_net_get_ip_route
 
 
 def ref_host():

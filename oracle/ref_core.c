@@ -14,7 +14,16 @@
  * exports entry points for the two static functions.  Nothing the reference references is stubbed:
  * the rest of core.c is unreachable from the export and dropped by
  * --gc-sections, and the library links with --no-undefined.
+ *
+ * The transmit side: net_push_iphdr and net_get_ip_route (core.c:592-626),
+ * both static, read `netcfg`, which core.c itself defines (core.c:23) and the
+ * entry points below set per call.  net_push_iphdr pushes onto an mbuf, built
+ * here by hand; the failed-BUG_ON handler of inc/net/mbuf.h, logk_bug, is the
+ * one symbol this file defines besides `iok`.  It is never reached (the mbuf
+ * has the headroom) and aborts.
  */
+#include <stdlib.h>
+
 #include REF_CORE_C
 
 struct iokernel_control iok;
@@ -42,4 +51,53 @@ __attribute__((visibility("default"))) int ref_ip_hdr_supported(const uint8_t *h
 
 	memcpy(&ip, hdr, sizeof(ip));
 	return ip_hdr_supported(&ip);
+}
+
+void logk_bug(bool fatal, const char *expr, const char *file, int line, const char *func)
+{
+	abort();
+}
+
+/* net_push_iphdr(m, proto, daddr, saddr, aux) with netcfg.no_tx_offloads =
+ * @no_tx_offloads onto an mbuf that holds @l4bytes bytes (their content is
+ * not read).  @aux_mode 0: aux == NULL; 1: aux->has_ecn = @has_ecn,
+ * aux->ecn = @ecn.  @hdr gets the 20 header bytes. */
+__attribute__((visibility("default"))) int ref_net_push_iphdr(int no_tx_offloads, uint8_t proto,
+                                                              uint32_t daddr, uint32_t saddr,
+                                                              uint16_t l4bytes, int aux_mode,
+                                                              int has_ecn, uint8_t ecn,
+                                                              uint8_t hdr[20])
+{
+	static unsigned char buf[64];
+	struct aux_tx_pkt_data aux;
+	struct mbuf m;
+
+	if (l4bytes > 65535 - 20)
+		return -1;
+	memset(&m, 0, sizeof(m));
+	memset(&aux, 0, sizeof(aux));
+	memset(&netcfg, 0, sizeof(netcfg));
+	netcfg.no_tx_offloads = no_tx_offloads != 0;
+	aux.has_ecn = has_ecn != 0;
+	aux.ecn = ecn;
+	m.head = buf;
+	m.head_len = 65535;
+	m.data = buf + sizeof(buf);   /* the L4 bytes would lie behind; only their count is used */
+	m.len = l4bytes;
+	net_push_iphdr(&m, proto, daddr, saddr, aux_mode ? &aux : NULL);
+	if (m.data != buf + sizeof(buf) - 20 || m.len != l4bytes + 20u)
+		return -2;
+	memcpy(hdr, m.data, 20);
+	return 0;
+}
+
+/* net_get_ip_route(daddr) with netcfg.addr/netmask/gateway as given (host order) */
+__attribute__((visibility("default"))) uint32_t ref_net_get_ip_route(uint32_t addr, uint32_t netmask,
+                                                                     uint32_t gateway, uint32_t daddr)
+{
+	memset(&netcfg, 0, sizeof(netcfg));
+	netcfg.addr = addr;
+	netcfg.netmask = netmask;
+	netcfg.gateway = gateway;
+	return net_get_ip_route(daddr);
 }

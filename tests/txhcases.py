@@ -1,6 +1,7 @@
 """Cases and a model of gcl_tx_hdr (include/gclassify.h), written from the
 rule's text and the reference's transmit path (runtime/net/udp.c:24-40,
-tcp_out.c:54-81, core.c:504-538, 581-626, 686-737), not from the C.
+tcp_out.c:54-81, core.c:504-538, 581-626, 686-737), not from the C;
+tests/test_txpath_ref.py holds it to bytes the reference's own code produced.
 
 A case is a dict: desc (TXH_DESC_DTYPE[m]), frame_off (u64[m]), frames_len,
 net (a dict of txh_net()'s arguments), cap, shm_base, neigh (a list of (ip,
