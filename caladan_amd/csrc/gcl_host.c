@@ -10,6 +10,7 @@
 #include "../../include/gclassify.h"
 #include "gcl_pay.h"
 #include "gcl_seg.h"
+#include "gcl_tcprx.h"
 #include "gcl_txh.h"
 
 #define ROT(x, k) (((x) << (k)) | ((x) >> (32 - (k))))
@@ -565,6 +566,141 @@ int gcl_tx_seg_host(const struct gcl_seg_in *in, const struct gcl_seg_out *out, 
 	*out->total_bytes = bytes;
 	if (counts)
 		for (int k = 0; k < GCL_SEGC_NR; k++)
+			counts[k] += c[k];
+	return 0;
+}
+
+/* One list entry of gcl_tcp_rx: the frame's bytes [12, 52) as dwords and
+ * gcl_pay_rule's word on them.  Returns the cookie of a TCP segment, or
+ * GCL_TCPRX_NONE. */
+static uint32_t tcprx_entry(const struct gcl_batch *b, const struct gcl_tcprx_in *in, uint64_t j,
+                            struct gcl_tcprx_seg *s)
+{
+	const uint64_t i = in->order ? in->order[j] : j;
+
+	if (i >= b->n)
+		return GCL_TCPRX_NONE;
+	const uint64_t raw = b->offs ? b->offs[i] : i * b->stride;
+	const uint64_t o = raw < b->frames_len ? raw : b->frames_len;
+	const uint64_t avail = b->frames_len - o;
+	const uint64_t L = b->pkt_len[i] < avail ? b->pkt_len[i] : avail;
+	uint8_t h[52] = {0};
+	uint32_t d[10];
+
+	if (avail)
+		memcpy(h, b->frames + o, avail < sizeof(h) ? avail : sizeof(h));
+	for (int x = 0; x < 10; x++)
+		d[x] = h[12 + 4 * x] | (uint32_t)h[13 + 4 * x] << 8 | (uint32_t)h[14 + 4 * x] << 16 |
+		       (uint32_t)h[15 + 4 * x] << 24;
+	const struct gcl_pay_desc r = gcl_pay_rule(d, o, L, in->l4_status != NULL,
+	                                           in->l4_status ? in->l4_status[i] : 0, 1, in->sock[i]);
+	if (r.kind != GCL_PAY_TCP)
+		return GCL_TCPRX_NONE;
+	*s = gcl_tcprx_parse(d, r.len);
+	return in->sock[i];
+}
+
+/* The rule of gcl_tcp_rx (gclassify.h) on the CPU: one walk over the list with
+ * every connection's live words kept in out_conn, gcl_tcprx_one of gcl_tcprx.h
+ * for every segment; then the layout, and a second walk for dst_off. */
+int gcl_tcp_rx_host(const struct gcl_batch *b, const struct gcl_tcprx_in *in,
+                    const struct gcl_tcprx_out *out, uint64_t *counts)
+{
+	uint64_t c[GCL_TCPRXC_NR] = {0}, at = 0;
+
+	if (!b || !in || !out || in->size != sizeof(*in) || !gcl_pay_align_ok(in->align) ||
+	    (!in->order && in->m != b->n) || in->m > (1ull << 31) || in->nconn > GCL_TCPRX_MAX_CONN ||
+	    in->blocks > GCL_TCPRX_MAX_BLOCKS || !in->sock || !out->conn_off)
+		return -EINVAL;
+	if (in->nconn && (!in->conn || !out->out_conn))
+		return -EINVAL;
+	if (in->m && (!out->verdict || !out->sflags || !out->rcv_nxt_after || !out->copy_len || !out->dst_off))
+		return -EINVAL;
+	if (((uintptr_t)in->order & 3) || ((uintptr_t)in->sock & 3) || ((uintptr_t)in->conn & 15) ||
+	    ((uintptr_t)out->rcv_nxt_after & 3) || ((uintptr_t)out->copy_len & 1) || ((uintptr_t)out->dst_off & 7) ||
+	    ((uintptr_t)out->out_conn & 15) || ((uintptr_t)out->conn_off & 7) || ((uintptr_t)counts & 7))
+		return -EINVAL;
+	if (in->m && (!b->frames || b->frames_len == UINT64_MAX || b->n > (1ull << 40) ||
+	              (!b->offs && (b->stride < 16 || (b->stride & 15) || b->stride > (1u << 20))) ||
+	              !b->pkt_len || ((uintptr_t)b->pkt_len & 1)))
+		return -EINVAL;
+	const uint32_t amask = in->align ? in->align - 1 : 0;
+
+	for (uint32_t k = 0; k < in->nconn; k++) {
+		const struct gcl_tcp_conn *cn = &in->conn[k];
+		struct gcl_tcp_conn_out *o = &out->out_conn[k];
+
+		memset(o, 0, sizeof(*o));
+		o->snd_una = cn->snd_una;
+		o->snd_wnd = cn->snd_wnd;
+		o->snd_wl1 = cn->snd_wl1;
+		o->snd_wl2 = cn->snd_wl2;
+		o->rcv_nxt = cn->rcv_nxt;
+		o->rcv_wnd = cn->rcv_wnd;
+		o->first_slow = GCL_TCPRX_NONE;
+		o->acks_delayed_cnt = cn->acks_delayed_cnt;
+		o->flags = cn->flags & (GCL_TCPC_RXQ | GCL_TCPC_ACK_DELAYED);
+	}
+	for (uint64_t j = 0; j < in->m; j++) {
+		struct gcl_tcprx_seg s = {0, 0, 0, 0, 0};
+		const uint32_t k = tcprx_entry(b, in, j, &s);
+		uint32_t verdict, sf = 0, after = 0, len = 0;
+
+		if (k == GCL_TCPRX_NONE) {
+			verdict = GCL_TCPRX_NA;
+		} else if (k >= in->nconn) {
+			verdict = GCL_TCPRX_NOCONN;
+		} else if (s.len > in->conn[k].rcv_mss) {
+			verdict = GCL_TCPRX_DROP;
+		} else {
+			struct gcl_tcp_conn_out *o = &out->out_conn[k];
+			struct gcl_tcprx_live l = {o->snd_una, o->snd_wnd, o->snd_wl1, o->snd_wl2, o->rcv_nxt,
+			                           o->rcv_wnd, o->acks_delayed_cnt, o->flags};
+			const int stopped = (l.flags & GCL_TCPO_STOPPED) != 0;
+
+			verdict = gcl_tcprx_one(&in->conn[k], &l, &s, &sf);
+			if (verdict == GCL_TCPRX_FAST) {
+				o->snd_una = l.snd_una;
+				o->snd_wnd = l.snd_wnd;
+				o->snd_wl1 = l.snd_wl1;
+				o->snd_wl2 = l.snd_wl2;
+				o->rcv_nxt = l.rcv_nxt;
+				o->rcv_wnd = l.rcv_wnd;
+				o->acks_delayed_cnt = (uint8_t)l.cnt;
+				o->nfast++;
+				o->nacks += (sf & GCL_TCPRX_SF_ACK_NOW) != 0;
+				after = l.rcv_nxt;
+				len = s.len;
+				c[GCL_TCPRXC_BYTES] += len;
+				c[GCL_TCPRXC_ACKS] += (sf & GCL_TCPRX_SF_ACK_NOW) != 0;
+				c[GCL_TCPRXC_WAKES] += (sf & GCL_TCPRX_SF_WAKE) != 0;
+			} else {
+				o->nslow++;
+				if (!stopped)
+					o->first_slow = (uint32_t)j;
+			}
+			o->flags = (uint8_t)l.flags;
+		}
+		out->verdict[j] = (uint8_t)verdict;
+		out->sflags[j] = (uint8_t)sf;
+		out->rcv_nxt_after[j] = after;
+		out->copy_len[j] = (uint16_t)len;
+		/* for now the offset inside the connection's region */
+		out->dst_off[j] = verdict == GCL_TCPRX_FAST ? (uint32_t)(s.seq - in->conn[k].rcv_nxt) : 0;
+		c[verdict]++;
+	}
+	for (uint32_t k = 0; k < in->nconn; k++) {
+		out->conn_off[k] = at;
+		at += gcl_tcprx_pad((uint32_t)(out->out_conn[k].rcv_nxt - in->conn[k].rcv_nxt), amask);
+	}
+	out->conn_off[in->nconn] = at;
+	for (uint64_t j = 0; j < in->m; j++)
+		if (out->verdict[j] == GCL_TCPRX_FAST) {
+			const uint64_t i = in->order ? in->order[j] : j;
+			out->dst_off[j] += out->conn_off[in->sock[i]];
+		}
+	if (counts)
+		for (int k = 0; k < GCL_TCPRXC_NR; k++)
 			counts[k] += c[k];
 	return 0;
 }

@@ -1,0 +1,785 @@
+/*
+ * gcl_tcprx.hip - tcp_rx_conn's established fast path for one runtime's list
+ * of packets (gcl_tcp_rx, gclassify.h; runtime/net/tcp_in.c:197-296): every
+ * connection's segments, in arrival order, through the rule of gcl_tcprx.h,
+ * the same inline code the host twin runs, and the layout that puts the bytes
+ * a connection accepted in one piece.
+ *
+ * Launches on the stream, ordered by the stream alone: no block waits for
+ * another, there is no look-back, flag or cooperative launch, and the only
+ * atomics are counter additions whose order changes nothing.
+ *
+ *   parse    one lane per list entry: order[j], the per-packet arrays, the
+ *            frame's bytes [12, 52) with gcl_payload.hip's loads (the 16-B
+ *            chunks of an aligned 64-B window, else byte by byte), then
+ *            gcl_pay_rule.  An entry that is NA, NOCONN or DROP gets its final
+ *            outputs here and the cookie GCL_TCPRX_NONE in the workspace; a
+ *            segment that takes part gets its cookie and one 16-B record
+ *            (seq, ack, win | flags << 16, len).
+ *   group    a stable LSD counting sort of the list positions that take part
+ *            by cookie, 11 bits a pass: one pass for nconn <= 2048, two up to
+ *            2^20.  As in gcl_plan.hip a pass is count (a wave per contiguous
+ *            range, its counters in LDS), three scan launches over
+ *            hist[digit][range], and scatter: a wave re-reads its range in
+ *            order, a lane's rank among the equal keys of its 64 entries is a
+ *            ballot population count, and the wave's leader lanes move its
+ *            counters on.  No atomic hands out a position, so arrival order
+ *            inside a connection is exact.  The first pass skips the entries
+ *            that do not take part, so the second runs over T <= m positions.
+ *   runs     one lane per sorted position: a position whose neighbour has
+ *            another cookie stores its connection's run start or end (one
+ *            writer each; the array is cleared by a memset on the stream).
+ *   walk     one wave per connection.  It gathers up to 64 records of the run
+ *            at once, evaluates the terms nothing moves in parallel, forms the
+ *            expected seq and the remaining window by a wave prefix sum of len
+ *            and finds the first lane that breaks the chain; only the send
+ *            window words and the delayed-ACK counter are carried serially,
+ *            wave-uniform, across that FAST prefix, with the segment's words
+ *            read out of their lane.  Longer runs loop in chunks of 64.  It
+ *            writes the per-entry outputs (dst_off relative to the run), the
+ *            connection's out_conn and its WAKE count; a connection without a
+ *            run writes its input back.
+ *   layout   three scan launches over pad(fast_bytes) write conn_off, one
+ *            launch adds conn_off[c] to the FAST entries' dst_off, and one
+ *            (only with counts) sums the connections' counters: an add per
+ *            counter per block.
+ *
+ * Bounds.  A list index is used only below m, a packet index only below n, a
+ * cookie only below nconn (parse leaves no other in the workspace, and every
+ * later use clamps again); sorted positions are stored only below m; the
+ * frame is read as in gcl_payload.hip: an aligned window only when it lies
+ * inside frames[0, frames_len), else every byte's index is tested.  Nothing is
+ * written outside the m-element outputs, out_conn[0, nconn), conn_off[0,
+ * nconn], counts and the workspace.  No inline assembly beyond compiler
+ * barriers.
+ */
+#include <errno.h>
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../../include/gclassify.h"
+#include "gcl_ctx.h"
+#include "gcl_pay.h"
+#include "gcl_tcprx.h"
+
+namespace gclk {
+
+constexpr uint32_t kRxThreads = 256;
+constexpr uint32_t kRxWaves = kRxThreads / 64;
+constexpr uint32_t kRxDigitBits = 11;
+constexpr uint32_t kRxDigits = 1u << kRxDigitBits; /* counters of one wave */
+constexpr uint32_t kRxChunk = 2048;                /* entries per scan block */
+constexpr uint32_t kRxTopThreads = 1024;
+constexpr uint32_t kRxBlocksPerCu = 4;
+
+struct RxParams {
+	const uint8_t *frames;
+	uint64_t frames_len;
+	uint64_t stride;
+	const uint64_t *offs;
+	const uint16_t *pkt_len;
+	uint64_t n;
+	const uint32_t *order;
+	const uint32_t *sock;
+	const uint8_t *l4_status;
+	const uint4 *conn;      /* struct gcl_tcp_conn as three 16-B words */
+	uint8_t *verdict, *sflags;
+	uint32_t *after;
+	uint16_t *copy_len;
+	uint64_t *dst_off;
+	uint4 *out_conn;        /* struct gcl_tcp_conn_out as three 16-B words */
+	unsigned long long *conn_off;
+	unsigned long long *counts;
+	/* the workspace */
+	uint4 *rec;             /* [m] */
+	uint32_t *cookie;       /* [m] */
+	uint32_t *idx[2];       /* [m] each: the sorted list positions of pass 0 and 1 */
+	uint32_t *hist;         /* [digits][ranges] */
+	uint32_t *csum;         /* [scan blocks] */
+	unsigned long long *lsum; /* [layout scan blocks] */
+	uint32_t *tot;          /* the number of entries that take part */
+	uint2 *run;             /* [nconn]: a connection's sorted positions [x, y) */
+	uint32_t *wakes;        /* [nconn] */
+	uint64_t m;             /* <= 2^31 */
+	uint32_t nconn;
+	uint32_t ranges, range_len; /* range_len: a multiple of 64 */
+	uint32_t amask;
+};
+
+/* ---- the exclusive scan of io.load(0 .. total), kRxChunk entries per block ---- */
+
+template <typename T, int NT>
+__device__ __forceinline__ T rx_block_scan(T x, T *total)
+{
+	__shared__ T sh[NT];
+	const uint32_t t = threadIdx.x;
+	T acc = x;
+
+	sh[t] = acc;
+	__syncthreads();
+	for (uint32_t d = 1; d < NT; d <<= 1) {
+		const T y = t >= d ? sh[t - d] : 0;
+		__syncthreads();
+		acc += y;
+		sh[t] = acc;
+		__syncthreads();
+	}
+	if (total)
+		*total = sh[NT - 1];
+	return acc - x;
+}
+
+/* hist in place; the grand total to *tot */
+struct RxHistIo {
+	typedef uint32_t T;
+	uint32_t *h, *tot;
+	__device__ T load(uint32_t i) const { return h[i]; }
+	__device__ void store(uint32_t i, T v) const { h[i] = v; }
+	__device__ void store_total(T v) const { *tot = v; }
+};
+
+/* pad(fast_bytes) of the connections -> conn_off[0, nconn], the total last */
+struct RxConnIo {
+	typedef unsigned long long T;
+	const uint4 *conn, *out_conn;
+	unsigned long long *conn_off;
+	uint32_t nconn, amask;
+	__device__ T load(uint32_t c) const
+	{
+		/* rcv_nxt: word 5 of gcl_tcp_conn, word 4 of gcl_tcp_conn_out */
+		return gcl_tcprx_pad(out_conn[3 * (size_t)c + 1].x - conn[3 * (size_t)c + 1].y, amask);
+	}
+	__device__ void store(uint32_t c, T v) const { conn_off[c] = v; }
+	__device__ void store_total(T v) const { conn_off[nconn] = v; }
+};
+
+template <typename Io>
+__global__ void __launch_bounds__(kRxThreads) rx_scan_sum_kernel(Io io, uint32_t total, typename Io::T *csum)
+{
+	typedef typename Io::T T;
+	const uint32_t i0 = blockIdx.x * kRxChunk + threadIdx.x * 8;
+	T s = 0, tot;
+
+	for (uint32_t j = 0; j < 8; j++)
+		s += i0 + j < total ? io.load(i0 + j) : 0;
+	(void)rx_block_scan<T, kRxThreads>(s, &tot);
+	if (threadIdx.x == 0)
+		csum[blockIdx.x] = tot;
+}
+
+/* one block: csum[0, nchunks) -> its exclusive scan, and the grand total */
+template <typename Io>
+__global__ void __launch_bounds__(kRxTopThreads) rx_scan_top_kernel(Io io, typename Io::T *csum, uint32_t nchunks)
+{
+	typedef typename Io::T T;
+	const uint32_t per = (nchunks + kRxTopThreads - 1) / kRxTopThreads;
+	const uint32_t i0 = threadIdx.x * per;
+	T s = 0;
+
+	for (uint32_t j = 0; j < per; j++)
+		s += i0 + j < nchunks ? csum[i0 + j] : 0;
+	T acc = rx_block_scan<T, kRxTopThreads>(s, nullptr);
+	for (uint32_t j = 0; j < per; j++) {
+		if (i0 + j < nchunks) {
+			const T x = csum[i0 + j];
+			csum[i0 + j] = acc;
+			acc += x;
+		}
+	}
+	if (threadIdx.x == kRxTopThreads - 1)
+		io.store_total(acc);
+}
+
+template <typename Io>
+__global__ void __launch_bounds__(kRxThreads) rx_scan_apply_kernel(Io io, uint32_t total, const typename Io::T *csum)
+{
+	typedef typename Io::T T;
+	const uint32_t i0 = blockIdx.x * kRxChunk + threadIdx.x * 8;
+	T x[8], s = 0;
+
+	for (uint32_t j = 0; j < 8; j++) {
+		x[j] = i0 + j < total ? io.load(i0 + j) : 0;
+		s += x[j];
+	}
+	T acc = csum[blockIdx.x] + rx_block_scan<T, kRxThreads>(s, nullptr);
+	for (uint32_t j = 0; j < 8; j++) {
+		if (i0 + j < total) {
+			io.store(i0 + j, acc);
+			acc += x[j];
+		}
+	}
+}
+
+/* ---- parse ---- */
+
+/* frame dwords 3..12 out of the window's sixteen, the frame starting 4 L bytes in */
+template <int L>
+__device__ __forceinline__ void rx_pick(const uint4 (&w)[4], uint32_t d[10])
+{
+	const uint32_t W[16] = {w[0].x, w[0].y, w[0].z, w[0].w, w[1].x, w[1].y, w[1].z, w[1].w,
+	                        w[2].x, w[2].y, w[2].z, w[2].w, w[3].x, w[3].y, w[3].z, w[3].w};
+#pragma unroll
+	for (int i = 0; i < 10; i++)
+		d[i] = W[3 + i + L];
+}
+
+__global__ void __launch_bounds__(kRxThreads) rx_parse_kernel(RxParams k)
+{
+	const uint32_t fbase = (uint32_t)(uintptr_t)k.frames;
+	uint32_t cnt[3] = {0, 0, 0}; /* DROP, NOCONN, NA: wave-uniform */
+
+	for (uint64_t j0 = (uint64_t)blockIdx.x * kRxThreads; j0 < k.m; j0 += (uint64_t)gridDim.x * kRxThreads) {
+		const uint64_t j = j0 + threadIdx.x;
+		uint32_t verdict = GCL_TCPRX_FAST; /* here: takes part, or no entry */
+		if (j < k.m) {
+			const uint64_t i = k.order ? k.order[j] : j;
+			uint32_t ck = GCL_TCPRX_NONE;
+			struct gcl_tcprx_seg s = {0, 0, 0, 0, 0};
+			if (i < k.n) {
+				const uint32_t st = k.l4_status ? k.l4_status[i] : 0;
+				const uint32_t sk = k.sock[i];
+				const uint64_t off = k.offs ? k.offs[i] : i * k.stride;
+				const uint64_t o = off < k.frames_len ? off : k.frames_len;
+				const uint64_t avail = k.frames_len - o;
+				const uint64_t L = k.pkt_len[i] < avail ? k.pkt_len[i] : avail;
+				const uint32_t lead = (fbase + (uint32_t)o) & 15;
+				const bool al = (lead & 3) == 0 && o >= lead && k.frames_len >= 64 &&
+				                o - lead <= k.frames_len - 64;
+				uint32_t d[10];
+				if (al) {
+					/* window dword x is frame dword x - lead / 4; wanted are 3..12 */
+					const uint4 *w = (const uint4 *)(k.frames + (o - lead));
+					uint4 c[4];
+					c[0] = make_uint4(0, 0, 0, 0);
+					if (lead == 0)
+						c[0] = w[0];
+					c[1] = w[1];
+					c[2] = w[2];
+					c[3] = w[3];
+					if (lead == 0)
+						rx_pick<0>(c, d);
+					else if (lead == 4)
+						rx_pick<1>(c, d);
+					else if (lead == 8)
+						rx_pick<2>(c, d);
+					else
+						rx_pick<3>(c, d);
+				} else {
+					const uint8_t *f = k.frames + o;
+					for (uint32_t x = 0; x < 10; x++) {
+						uint32_t v = 0;
+						for (uint32_t y = 0; y < 4; y++) {
+							const uint32_t at = 12 + 4 * x + y;
+							v |= (at < avail ? (uint32_t)f[at] : 0u) << (8 * y);
+						}
+						d[x] = v;
+					}
+				}
+				const struct gcl_pay_desc r = gcl_pay_rule(d, o, L, k.l4_status != nullptr, st, 1, sk);
+				if (r.kind == GCL_PAY_TCP) {
+					ck = sk;
+					s = gcl_tcprx_parse(d, r.len);
+				}
+			}
+			if (ck == GCL_TCPRX_NONE) {
+				verdict = GCL_TCPRX_NA;
+			} else if (ck >= k.nconn) {
+				verdict = GCL_TCPRX_NOCONN;
+			} else {
+				const uint32_t mss = k.conn[3 * (size_t)ck + 1].w & 0xFFFFu; /* rcv_mss */
+				if (s.len > mss)
+					verdict = GCL_TCPRX_DROP;
+			}
+			if (verdict != GCL_TCPRX_FAST) {
+				k.verdict[j] = (uint8_t)verdict;
+				k.sflags[j] = 0;
+				k.after[j] = 0;
+				k.copy_len[j] = 0;
+				k.dst_off[j] = 0;
+				ck = GCL_TCPRX_NONE;
+			} else {
+				k.rec[j] = make_uint4(s.seq, s.ack, s.win | s.flags << 16, s.len);
+			}
+			k.cookie[j] = ck;
+		}
+		cnt[0] += (uint32_t)__popcll(__ballot(verdict == GCL_TCPRX_DROP));
+		cnt[1] += (uint32_t)__popcll(__ballot(verdict == GCL_TCPRX_NOCONN));
+		cnt[2] += (uint32_t)__popcll(__ballot(verdict == GCL_TCPRX_NA));
+	}
+	if (k.counts && (threadIdx.x & 63) == 0) {
+		if (cnt[0])
+			atomicAdd(k.counts + GCL_TCPRXC_DROP, (unsigned long long)cnt[0]);
+		if (cnt[1])
+			atomicAdd(k.counts + GCL_TCPRXC_NOCONN, (unsigned long long)cnt[1]);
+		if (cnt[2])
+			atomicAdd(k.counts + GCL_TCPRXC_NA, (unsigned long long)cnt[2]);
+	}
+}
+
+/* ---- group ---- */
+
+struct RxPass {
+	const uint32_t *src; /* NULL: the list itself, entries that do not take part skipped */
+	uint32_t *dst;
+	uint32_t shift, nb, kbits;
+};
+
+/* the lanes of this wave that are @valid and hold this lane's @key */
+__device__ __forceinline__ uint64_t rx_match(uint32_t key, bool valid, uint32_t kbits)
+{
+	uint64_t m = __ballot(valid);
+
+	for (uint32_t b = 0; b < kbits; b++) {
+		const bool bit = (key >> b) & 1u;
+		const uint64_t bal = __ballot(bit);
+		m &= bit ? bal : ~bal;
+	}
+	return m;
+}
+
+/* source position p of a pass: the list position it names and its digit */
+__device__ __forceinline__ bool rx_key(const RxParams &k, const RxPass &ps, uint64_t p, uint64_t end,
+                                       uint32_t *j, uint32_t *key)
+{
+	bool valid = p < end;
+	uint32_t at = 0, ck = GCL_TCPRX_NONE;
+
+	if (valid) {
+		at = ps.src ? ps.src[p] : (uint32_t)p;
+		valid = at < k.m;
+	}
+	if (valid) {
+		ck = k.cookie[at];
+		valid = ck < k.nconn;
+	}
+	const uint32_t dg = valid ? (ck >> ps.shift) & (kRxDigits - 1) : 0;
+	*j = at;
+	*key = dg < ps.nb ? dg : ps.nb - 1;
+	return valid;
+}
+
+__device__ __forceinline__ uint64_t rx_limit(const RxParams &k, const RxPass &ps)
+{
+	const uint64_t t = ps.src ? *k.tot : k.m;
+	return t < k.m ? t : k.m;
+}
+
+__global__ void __launch_bounds__(kRxThreads) rx_count_kernel(RxParams k, RxPass ps)
+{
+	__shared__ uint32_t lds[kRxWaves][kRxDigits];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	const uint32_t r = blockIdx.x * kRxWaves + wave;
+
+	if (r >= k.ranges)
+		return; /* waves share nothing: no barrier below */
+	uint32_t *cnt = lds[wave];
+	for (uint32_t b = lane; b < ps.nb; b += 64)
+		cnt[b] = 0;
+	const uint64_t limit = rx_limit(k, ps);
+	const uint64_t start = (uint64_t)r * k.range_len;
+	const uint64_t end = start + k.range_len < limit ? start + k.range_len : limit;
+	for (uint64_t base = start; base < end; base += 64) {
+		uint32_t j, key;
+		const bool valid = rx_key(k, ps, base + lane, end, &j, &key);
+		const uint64_t mt = rx_match(key, valid, ps.kbits);
+		/* one add per distinct key of the step, by its lowest lane */
+		if (valid && !(mt & ((1ull << lane) - 1)))
+			atomicAdd(&cnt[key], (uint32_t)__popcll(mt));
+	}
+	asm volatile("" ::: "memory");
+	/* every entry of this range's column is written: no zeroing of the workspace */
+	for (uint32_t b = lane; b < ps.nb; b += 64)
+		k.hist[(size_t)b * k.ranges + r] = cnt[b];
+}
+
+__global__ void __launch_bounds__(kRxThreads) rx_scatter_kernel(RxParams k, RxPass ps)
+{
+	__shared__ uint32_t lds[kRxWaves][kRxDigits];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	const uint32_t r = blockIdx.x * kRxWaves + wave;
+
+	if (r >= k.ranges)
+		return;
+	/* read and moved on by different lanes from step to step: LDS serves one
+	 * wave's accesses in issue order, and volatile keeps the compiler to it */
+	volatile uint32_t *cnt = lds[wave];
+	const uint64_t limit = rx_limit(k, ps);
+	const uint64_t start = (uint64_t)r * k.range_len;
+	const uint64_t end = start + k.range_len < limit ? start + k.range_len : limit;
+
+	if (start >= end)
+		return;
+	for (uint32_t b = lane; b < ps.nb; b += 64)
+		cnt[b] = k.hist[(size_t)b * k.ranges + r];
+	for (uint64_t base = start; base < end; base += 64) {
+		uint32_t j, key;
+		const bool valid = rx_key(k, ps, base + lane, end, &j, &key);
+		const uint64_t mt = rx_match(key, valid, ps.kbits);
+		const uint32_t rank = (uint32_t)__popcll(mt & ((1ull << lane) - 1));
+		const uint32_t at = cnt[key]; /* key < nb <= kRxDigits, whatever the bytes */
+		if (valid) {
+			const uint32_t pos = at + rank;
+			if (pos < k.m)
+				ps.dst[pos] = j;
+			if (rank == 0)
+				cnt[key] = at + (uint32_t)__popcll(mt);
+		}
+		asm volatile("" ::: "memory");
+	}
+}
+
+/* ---- runs ---- */
+
+__global__ void __launch_bounds__(kRxThreads) rx_runs_kernel(RxParams k, const uint32_t *sorted)
+{
+	const uint64_t t = *k.tot < k.m ? *k.tot : k.m;
+
+	for (uint64_t p = (uint64_t)blockIdx.x * kRxThreads + threadIdx.x; p < t;
+	     p += (uint64_t)gridDim.x * kRxThreads) {
+		const uint32_t j = sorted[p], jp = p ? sorted[p - 1] : 0, jn = p + 1 < t ? sorted[p + 1] : 0;
+		const uint32_t c = j < k.m ? k.cookie[j] : GCL_TCPRX_NONE;
+		const uint32_t cp = p && jp < k.m ? k.cookie[jp] : GCL_TCPRX_NONE;
+		const uint32_t cn = p + 1 < t && jn < k.m ? k.cookie[jn] : GCL_TCPRX_NONE;
+		if (c < k.nconn) {
+			if (c != cp)
+				k.run[c].x = (uint32_t)p;
+			if (c != cn)
+				k.run[c].y = (uint32_t)p + 1;
+		}
+	}
+}
+
+/* ---- walk ---- */
+
+__device__ __forceinline__ uint32_t rx_lane(uint32_t v, uint32_t l)
+{
+	return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
+}
+
+__global__ void __launch_bounds__(kRxThreads) rx_walk_kernel(RxParams k, const uint32_t *sorted)
+{
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRxWaves + (threadIdx.x >> 6)));
+
+	if (c >= k.nconn)
+		return;
+	struct gcl_tcp_conn cn;
+	{
+		const uint4 a = k.conn[3 * (size_t)c], b = k.conn[3 * (size_t)c + 1], d = k.conn[3 * (size_t)c + 2];
+		cn.snd_una = a.x; cn.snd_nxt = a.y; cn.snd_wnd = a.z; cn.snd_wl1 = a.w;
+		cn.snd_wl2 = b.x; cn.rcv_nxt = b.y; cn.rcv_wnd = b.z;
+		cn.rcv_mss = (uint16_t)b.w; cn.snd_wscale = (uint8_t)(b.w >> 16); cn.flags = (uint8_t)(b.w >> 24);
+		cn.acks_delayed_cnt = (uint8_t)d.x;
+	}
+	struct gcl_tcprx_live l = gcl_tcprx_live_of(&cn);
+	const uint2 rn = k.run[c];
+	const uint64_t re = rn.y < k.m ? rn.y : k.m;
+	const uint64_t rs = rn.x < re ? rn.x : re;
+	uint32_t nfast = 0, nslow = 0, nacks = 0, wakes = 0, first_slow = GCL_TCPRX_NONE;
+
+	for (uint64_t base = rs; base < re; base += 64) { /* uniform */
+		const uint32_t nv = re - base < 64 ? (uint32_t)(re - base) : 64;
+		const bool valid = lane < nv;
+		uint32_t j = valid ? sorted[base + lane] : 0;
+		if (j >= k.m)
+			j = (uint32_t)(k.m - 1);
+		const uint4 rec = valid ? k.rec[j] : make_uint4(0, 0, 0, 0);
+		const uint32_t seq = rec.x, ack = rec.y, win = rec.z & 0xFFFFu, flags = rec.z >> 16, len = rec.w;
+		const bool stopped = (l.flags & GCL_TCPO_STOPPED) != 0;
+
+		/* the sum of len over the lanes below: the chain's rcv_nxt and rcv_wnd at this lane */
+		uint32_t incl = len;
+		for (int d = 1; d < 64; d <<= 1) {
+			const uint32_t u = (uint32_t)__shfl_up((int)incl, d);
+			if (lane >= (uint32_t)d)
+				incl += u;
+		}
+		const uint32_t excl = incl - len;
+		const bool bad = !valid || gcl_tcprx_slow_fixed(flags, len, ack, cn.snd_nxt, cn.flags) ||
+		                 gcl_tcprx_slow_rcv(seq, len, l.rcv_nxt + excl, l.rcv_wnd - excl);
+		const uint64_t badmask = __ballot(bad);
+		uint32_t F = stopped ? 0 : badmask ? (uint32_t)__builtin_ctzll(badmask) : 64;
+
+		uint32_t sf_mine = 0, after_mine = 0;
+		for (uint32_t x = 0; x < F; x++) { /* uniform: the words that are carried serially */
+			if (gcl_tcprx_snd_full(l.snd_una, l.snd_wnd, cn.snd_nxt)) {
+				F = x;
+				break;
+			}
+			uint32_t sf = gcl_tcprx_ack_step(&l, rx_lane(seq, x), rx_lane(ack, x),
+			                                 rx_lane(win, x) << (cn.snd_wscale & 31));
+			sf |= gcl_tcprx_rx_step(&l, rx_lane(len, x), rx_lane(flags, x));
+			if (lane == x) {
+				sf_mine = sf;
+				after_mine = l.rcv_nxt;
+			}
+			nacks += (sf & GCL_TCPRX_SF_ACK_NOW) != 0;
+			wakes += (sf & GCL_TCPRX_SF_WAKE) != 0;
+		}
+		nfast += F;
+		nslow += nv - F;
+		if (F < nv) {
+			if (!stopped)
+				first_slow = rx_lane(j, F);
+			l.flags |= GCL_TCPO_STOPPED;
+		}
+		if (valid) {
+			const bool fast = lane < F;
+			k.verdict[j] = (uint8_t)(fast ? GCL_TCPRX_FAST : GCL_TCPRX_SLOW);
+			k.sflags[j] = (uint8_t)sf_mine;
+			k.after[j] = after_mine;
+			k.copy_len[j] = (uint16_t)(fast ? len : 0);
+			k.dst_off[j] = fast ? (uint32_t)(seq - cn.rcv_nxt) : 0; /* layout adds conn_off[c] */
+		}
+	}
+	if (lane == 0) {
+		k.out_conn[3 * (size_t)c] = make_uint4(l.snd_una, l.snd_wnd, l.snd_wl1, l.snd_wl2);
+		k.out_conn[3 * (size_t)c + 1] = make_uint4(l.rcv_nxt, l.rcv_wnd, nfast, nslow);
+		k.out_conn[3 * (size_t)c + 2] = make_uint4(nacks, first_slow, (l.cnt & 0xFFu) | (l.flags & 0xFFu) << 8, 0);
+		k.wakes[c] = wakes;
+	}
+}
+
+/* ---- layout ---- */
+
+__global__ void __launch_bounds__(kRxThreads) rx_fix_kernel(RxParams k)
+{
+	for (uint64_t j = (uint64_t)blockIdx.x * kRxThreads + threadIdx.x; j < k.m;
+	     j += (uint64_t)gridDim.x * kRxThreads) {
+		const uint32_t c = k.cookie[j];
+		if (c < k.nconn && k.verdict[j] == GCL_TCPRX_FAST)
+			k.dst_off[j] += k.conn_off[c];
+	}
+}
+
+/* FAST, SLOW, BYTES, ACKS and WAKES of the call, summed over the connections */
+__global__ void __launch_bounds__(kRxThreads) rx_counts_kernel(RxParams k)
+{
+	__shared__ unsigned long long blk[5];
+	unsigned long long v[5] = {0, 0, 0, 0, 0};
+
+	if (threadIdx.x < 5)
+		blk[threadIdx.x] = 0;
+	__syncthreads();
+	for (uint32_t c = blockIdx.x * kRxThreads + threadIdx.x; c < k.nconn; c += gridDim.x * kRxThreads) {
+		const uint4 o1 = k.out_conn[3 * (size_t)c + 1], o2 = k.out_conn[3 * (size_t)c + 2];
+		v[0] += o1.z;
+		v[1] += o1.w;
+		v[2] += (uint32_t)(o1.x - k.conn[3 * (size_t)c + 1].y);
+		v[3] += o2.x;
+		v[4] += k.wakes[c];
+	}
+#pragma unroll
+	for (int x = 0; x < 5; x++) {
+		for (int d = 32; d; d >>= 1) {
+			const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v[x], d);
+			const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v[x] >> 32), d);
+			v[x] += (unsigned long long)hi << 32 | lo;
+		}
+		if ((threadIdx.x & 63) == 0 && v[x])
+			atomicAdd(&blk[x], v[x]);
+	}
+	__syncthreads();
+	if (threadIdx.x < 5 && blk[threadIdx.x]) {
+		const uint32_t slot[5] = {GCL_TCPRXC_FAST, GCL_TCPRXC_SLOW, GCL_TCPRXC_BYTES, GCL_TCPRXC_ACKS,
+		                          GCL_TCPRXC_WAKES};
+		atomicAdd(k.counts + slot[threadIdx.x], blk[threadIdx.x]);
+	}
+}
+
+/* ---- the workspace ---- */
+
+struct RxGeom {
+	uint32_t passes, nb[2], kbits[2];
+	uint32_t ranges; /* as sized: in->blocks or the cap */
+	size_t rec, cookie, idx[2], hist, csum, lsum, tot, run, wakes, bytes;
+};
+
+static size_t rx_up16(size_t x)
+{
+	return (x + 15) & ~(size_t)15;
+}
+
+static uint32_t rx_bits(uint32_t nb)
+{
+	return nb > 1 ? 32 - (uint32_t)__builtin_clz(nb - 1) : 0;
+}
+
+static int rx_geometry(uint64_t m, uint32_t nconn, uint32_t blocks, RxGeom *g)
+{
+	if (m > (1ull << 31) || nconn > GCL_TCPRX_MAX_CONN || blocks > GCL_TCPRX_MAX_BLOCKS)
+		return -EINVAL;
+	g->passes = nconn > kRxDigits ? 2 : 1;
+	g->nb[0] = nconn > kRxDigits ? kRxDigits : nconn ? nconn : 1;
+	g->nb[1] = g->passes == 2 ? ((nconn - 1) >> kRxDigitBits) + 1 : 0;
+	g->kbits[0] = rx_bits(g->nb[0]);
+	g->kbits[1] = rx_bits(g->nb[1]);
+	/* the library's choice never exceeds one range per 256 entries, nor the cap */
+	const uint64_t tiles = (m + kRxThreads - 1) / kRxThreads;
+	g->ranges = blocks ? blocks : (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(tiles, GCL_TCPRX_MAX_BLOCKS));
+	const size_t entries = (size_t)std::max(g->nb[0], g->nb[1]) * g->ranges;
+	size_t at = 0;
+	g->rec = at;
+	at += 16 * (size_t)m;
+	g->cookie = at;
+	at += rx_up16(4 * (size_t)m);
+	g->idx[0] = at;
+	at += rx_up16(4 * (size_t)m);
+	g->idx[1] = at;
+	at += g->passes == 2 ? rx_up16(4 * (size_t)m) : 0;
+	g->hist = at;
+	at += 4 * entries;
+	g->csum = at;
+	at += rx_up16(4 * ((entries + kRxChunk - 1) / kRxChunk));
+	g->lsum = at;
+	at += rx_up16(8 * (((size_t)nconn + kRxChunk - 1) / kRxChunk));
+	g->tot = at;
+	at += 16;
+	g->run = at;
+	at += rx_up16(8 * (size_t)nconn);
+	g->wakes = at;
+	at += rx_up16(4 * (size_t)nconn);
+	g->bytes = at;
+	return 0;
+}
+
+static bool rx_misaligned(const void *p, uintptr_t a)
+{
+	return ((uintptr_t)p & (a - 1)) != 0;
+}
+
+} // namespace gclk
+
+using namespace gclk;
+
+extern "C" int gcl_tcp_rx_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, size_t *bytes)
+{
+	RxGeom g;
+
+	if (!bytes || rx_geometry(m, nconn, blocks, &g))
+		return -EINVAL;
+	*bytes = g.bytes;
+	return 0;
+}
+
+extern "C" int gcl_tcp_rx(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprx_in *in,
+                          const struct gcl_tcprx_out *out, uint64_t *counts, void *workspace,
+                          size_t workspace_bytes, void *hip_stream)
+{
+	hipStream_t s = (hipStream_t)hip_stream;
+	RxGeom g;
+
+	if (!c || !b || !in || !out || in->size != sizeof(*in) || !gcl_pay_align_ok(in->align) ||
+	    (!in->order && in->m != b->n) || rx_geometry(in->m, in->nconn, in->blocks, &g) || !in->sock ||
+	    !out->conn_off)
+		return -EINVAL;
+	if (in->nconn && (!in->conn || !out->out_conn))
+		return -EINVAL;
+	if (in->m && (!out->verdict || !out->sflags || !out->rcv_nxt_after || !out->copy_len || !out->dst_off))
+		return -EINVAL;
+	if (rx_misaligned(in->order, 4) || rx_misaligned(in->sock, 4) || rx_misaligned(in->conn, 16) ||
+	    rx_misaligned(out->rcv_nxt_after, 4) || rx_misaligned(out->copy_len, 2) ||
+	    rx_misaligned(out->dst_off, 8) || rx_misaligned(out->out_conn, 16) ||
+	    rx_misaligned(out->conn_off, 8) || rx_misaligned(counts, 8))
+		return -EINVAL;
+	if (!workspace || rx_misaligned(workspace, 16) || workspace_bytes < g.bytes)
+		return -EINVAL;
+	if (in->m && (!b->frames || b->frames_len == UINT64_MAX || b->n > (1ull << 40) ||
+	              (!b->offs && (b->stride < 16 || (b->stride & 15) || b->stride > (1u << 20))) ||
+	              !b->pkt_len || rx_misaligned(b->pkt_len, 2)))
+		return -EINVAL;
+	if (hipSetDevice(c->device) != hipSuccess)
+		return -EIO;
+	c->last_stream = s;
+
+	uint8_t *ws = (uint8_t *)workspace;
+	RxParams k;
+	k.frames = b->frames;
+	k.frames_len = b->frames_len;
+	k.stride = b->stride;
+	k.offs = b->offs;
+	k.pkt_len = b->pkt_len;
+	k.n = b->n;
+	k.order = in->order;
+	k.sock = in->sock;
+	k.l4_status = in->l4_status;
+	k.conn = (const uint4 *)in->conn;
+	k.verdict = out->verdict;
+	k.sflags = out->sflags;
+	k.after = out->rcv_nxt_after;
+	k.copy_len = out->copy_len;
+	k.dst_off = out->dst_off;
+	k.out_conn = (uint4 *)out->out_conn;
+	k.conn_off = (unsigned long long *)out->conn_off;
+	k.counts = (unsigned long long *)counts;
+	k.rec = (uint4 *)(ws + g.rec);
+	k.cookie = (uint32_t *)(ws + g.cookie);
+	k.idx[0] = (uint32_t *)(ws + g.idx[0]);
+	k.idx[1] = (uint32_t *)(ws + g.idx[1]);
+	k.hist = (uint32_t *)(ws + g.hist);
+	k.csum = (uint32_t *)(ws + g.csum);
+	k.lsum = (unsigned long long *)(ws + g.lsum);
+	k.tot = (uint32_t *)(ws + g.tot);
+	k.run = (uint2 *)(ws + g.run);
+	k.wakes = (uint32_t *)(ws + g.wakes);
+	k.m = in->m;
+	k.nconn = in->nconn;
+	k.amask = in->align ? in->align - 1 : 0;
+
+	const uint32_t cus = (uint32_t)(c->num_cus > 0 ? c->num_cus : 1);
+	const uint64_t tiles = (in->m + kRxThreads - 1) / kRxThreads;
+	const unsigned egrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)cus * 8));
+	k.ranges = in->blocks ? in->blocks :
+	           (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(tiles, std::min<uint32_t>(cus * kRxBlocksPerCu,
+	                                                                                      GCL_TCPRX_MAX_BLOCKS)));
+	k.range_len = (uint32_t)(((in->m + k.ranges - 1) / k.ranges + 63) / 64 * 64);
+	if (k.range_len == 0)
+		k.range_len = 64;
+
+	if (in->nconn == 0) { /* every TCP segment is NOCONN: nothing to group, walk or lay out */
+		if (in->m)
+			hipLaunchKernelGGL(rx_parse_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
+		if (hipMemsetAsync(out->conn_off, 0, sizeof(uint64_t), s) != hipSuccess)
+			return -EIO;
+		return hipGetLastError() == hipSuccess ? 0 : -EIO;
+	}
+	if (hipMemsetAsync(k.run, 0, 8 * (size_t)in->nconn, s) != hipSuccess)
+		return -EIO;
+	const uint32_t *sorted = k.idx[g.passes - 1];
+	if (in->m) {
+		hipLaunchKernelGGL(rx_parse_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
+		for (uint32_t p = 0; p < g.passes; p++) {
+			const RxPass ps = {p ? k.idx[0] : nullptr, k.idx[p], p * kRxDigitBits, g.nb[p], g.kbits[p]};
+			const RxHistIo io = {k.hist, k.tot};
+			const uint32_t total = ps.nb * k.ranges;
+			const uint32_t nchunks = (total + kRxChunk - 1) / kRxChunk;
+			const dim3 grid((k.ranges + kRxWaves - 1) / kRxWaves);
+			hipLaunchKernelGGL(rx_count_kernel, grid, dim3(kRxThreads), 0, s, k, ps);
+			hipLaunchKernelGGL(rx_scan_sum_kernel<RxHistIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, total, k.csum);
+			hipLaunchKernelGGL(rx_scan_top_kernel<RxHistIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, k.csum, nchunks);
+			hipLaunchKernelGGL(rx_scan_apply_kernel<RxHistIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, total,
+			                   k.csum);
+			hipLaunchKernelGGL(rx_scatter_kernel, grid, dim3(kRxThreads), 0, s, k, ps);
+		}
+		hipLaunchKernelGGL(rx_runs_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k, sorted);
+	}
+	hipLaunchKernelGGL(rx_walk_kernel, dim3((in->nconn + kRxWaves - 1) / kRxWaves), dim3(kRxThreads), 0, s, k,
+	                   sorted);
+	{
+		const RxConnIo io = {k.conn, k.out_conn, k.conn_off, in->nconn, k.amask};
+		const uint32_t nchunks = (in->nconn + kRxChunk - 1) / kRxChunk;
+		hipLaunchKernelGGL(rx_scan_sum_kernel<RxConnIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn, k.lsum);
+		hipLaunchKernelGGL(rx_scan_top_kernel<RxConnIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, k.lsum, nchunks);
+		hipLaunchKernelGGL(rx_scan_apply_kernel<RxConnIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn,
+		                   k.lsum);
+	}
+	if (in->m)
+		hipLaunchKernelGGL(rx_fix_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
+	if (counts)
+		hipLaunchKernelGGL(rx_counts_kernel,
+		                   dim3(std::min<uint32_t>((in->nconn + kRxThreads - 1) / kRxThreads, cus * 2)),
+		                   dim3(kRxThreads), 0, s, k);
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}

@@ -101,6 +101,24 @@ SEG_SEND_DTYPE = np.dtype([("lip", "<u4"), ("rip", "<u4"), ("lport", "<u2"), ("r
                            ("proto", "u1"), ("ecn", "u1"), ("mss", "<u2"), ("snd_nxt", "<u4"),
                            ("ack", "<u4"), ("win", "<u2"), ("pad", "<u2"), ("len", "<u4"),
                            ("winlen", "<u4"), ("pad2", "<u4"), ("src_off", "<u8")])
+# gcl_tcp_rx: the verdict byte (also the first counter slots), the counters, sflags, the connection
+# flags, the caps, struct gcl_tcp_conn and struct gcl_tcp_conn_out
+TCPRX_FAST, TCPRX_SLOW, TCPRX_DROP, TCPRX_NOCONN, TCPRX_NA = range(5)
+TCPRXC_BYTES, TCPRXC_ACKS, TCPRXC_WAKES, TCPRXC_NR = 5, 6, 7, 8
+TCPRX_SF_WAKE, TCPRX_SF_ACK_NOW, TCPRX_SF_ACKED, TCPRX_SF_WND = 0x01, 0x02, 0x04, 0x08
+TCPC_ELIGIBLE, TCPC_RXQ, TCPC_ACK_DELAYED = 0x01, 0x02, 0x04
+TCPO_STOPPED, TCPO_WOKEN, TCPO_TIMER_ARMED, TCPO_REP_ACKS_RESET = 0x08, 0x10, 0x20, 0x40
+TCPRX_MAX_BLOCKS, TCPRX_MAX_CONN, TCPRX_NONE = 1024, 1 << 20, 0xFFFFFFFF
+# its grouping (csrc/gcl_tcprx.hip): the connections one counting-sort pass serves
+TCPRX_PASS_CONN = 2048
+TCP_CONN_DTYPE = np.dtype([("snd_una", "<u4"), ("snd_nxt", "<u4"), ("snd_wnd", "<u4"), ("snd_wl1", "<u4"),
+                           ("snd_wl2", "<u4"), ("rcv_nxt", "<u4"), ("rcv_wnd", "<u4"), ("rcv_mss", "<u2"),
+                           ("snd_wscale", "u1"), ("flags", "u1"), ("acks_delayed_cnt", "u1"),
+                           ("pad", "u1", (15,))])
+TCP_CONN_OUT_DTYPE = np.dtype([("snd_una", "<u4"), ("snd_wnd", "<u4"), ("snd_wl1", "<u4"), ("snd_wl2", "<u4"),
+                               ("rcv_nxt", "<u4"), ("rcv_wnd", "<u4"), ("nfast", "<u4"), ("nslow", "<u4"),
+                               ("nacks", "<u4"), ("first_slow", "<u4"), ("acks_delayed_cnt", "u1"),
+                               ("flags", "u1"), ("pad", "u1", (6,))])
 STAT_NAMES = ["RX_UNREGISTERED_MAC", "RX_UNICAST_FAIL", "RX_BROADCAST_FAIL",
               "RX_FLOW_TAG_MATCH", "RX_UNHANDLED", "RX_HASH_MISSING", "RX_PULLED"]
 
@@ -339,6 +357,22 @@ class GclSegOut(ctypes.Structure):
     _fields_ = [(f, ctypes.c_void_p) for f in SEG_OUT_FIELDS]
 
 
+class GclTcprxIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("align", ctypes.c_uint32), ("order", ctypes.c_void_p),
+                ("m", ctypes.c_uint64), ("sock", ctypes.c_void_p), ("l4_status", ctypes.c_void_p),
+                ("conn", ctypes.c_void_p), ("nconn", ctypes.c_uint32), ("blocks", ctypes.c_uint32)]
+
+
+TCPRX_ENTRY_FIELDS = ("verdict", "sflags", "rcv_nxt_after", "copy_len", "dst_off")
+TCPRX_OUT_FIELDS = TCPRX_ENTRY_FIELDS + ("out_conn", "conn_off")
+
+
+class GclTcprxOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in TCPRX_OUT_FIELDS]
+
+
+assert ctypes.sizeof(GclTcprxIn) == 56 and ctypes.sizeof(GclTcprxOut) == 56
+assert TCP_CONN_DTYPE.itemsize == 48 and TCP_CONN_OUT_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclSegIn) == 64 and ctypes.sizeof(GclSegOut) == 104 and SEG_SEND_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclTxhIn) == 88 and ctypes.sizeof(GclTxhNet) == 20 and TXH_DESC_DTYPE.itemsize == 32
 assert NEIGH_ENTRY_DTYPE.itemsize == 12
@@ -439,6 +473,11 @@ def _load():
         "gcl_tx_seg": (i32, [vp, ctypes.POINTER(GclSegIn), ctypes.POINTER(GclSegOut), vp, vp,
                              ctypes.c_size_t, vp]),
         "gcl_tx_seg_host": (i32, [ctypes.POINTER(GclSegIn), ctypes.POINTER(GclSegOut), vp]),
+        "gcl_tcp_rx_workspace": (i32, [u64, u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_rx": (i32, [vp, ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxIn),
+                             ctypes.POINTER(GclTcprxOut), vp, vp, ctypes.c_size_t, vp]),
+        "gcl_tcp_rx_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxIn),
+                                  ctypes.POINTER(GclTcprxOut), vp]),
         "gcl_neigh_tbl_new": (vp, []),
         "gcl_neigh_tbl_free": (None, [vp]),
         "gcl_neigh_tbl_set": (i32, [vp, vp, u32]),
@@ -922,6 +961,65 @@ def tx_seg_workspace(m, blocks=0):
     """gcl_tx_seg_workspace: bytes of device scratch a call over @m writes takes."""
     need = ctypes.c_size_t()
     _check(lib.gcl_tx_seg_workspace(m, blocks, ctypes.byref(need)), "gcl_tx_seg_workspace")
+    return need.value
+
+
+def _tcprx_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status, conn, nconn,
+                   align, blocks, out, counts):
+    """The three structs of gcl_tcp_rx / gcl_tcp_rx_host, sizes checked; @out
+    maps TCPRX_OUT_FIELDS to buffers."""
+    if sock is None:
+        raise ValueError("sock is required")
+    for arr, w in ((offs, 8), (pkt_len, 2), (sock, 4), (l4_status, 1)):
+        if arr is not None and _nbytes(arr) < w * n:
+            raise ValueError("per-packet array too small")
+    for arr, w in ((order, 4), (out["verdict"], 1), (out["sflags"], 1), (out["rcv_nxt_after"], 4),
+                   (out["copy_len"], 2), (out["dst_off"], 8)):
+        if arr is not None and _nbytes(arr) < w * m:
+            raise ValueError("per-entry array too small")
+    for arr, w in ((conn, 48), (out["out_conn"], 48)):
+        if arr is not None and _nbytes(arr) < w * nconn:
+            raise ValueError("per-connection array too small")
+    if out["conn_off"] is not None and _nbytes(out["conn_off"]) < 8 * (nconn + 1):
+        raise ValueError("conn_off too small")
+    if counts is not None and _nbytes(counts) < 8 * TCPRXC_NR:
+        raise ValueError("counts buffer too small")
+    b = GclBatch(frames=_ptr(frames), frames_len=_frames_len(frames, frames_len), stride=stride,
+                 offs=_ptr(offs), olflags=None, rss=None, fdir_hi=None, pkt_len=_ptr(pkt_len), n=n,
+                 dst_hint=None)
+    rin = GclTcprxIn(size=ctypes.sizeof(GclTcprxIn), align=align, order=_ptr(order), m=m, sock=_ptr(sock),
+                     l4_status=_ptr(l4_status), conn=_ptr(conn), nconn=nconn, blocks=blocks)
+    rout = GclTcprxOut(**{f: _ptr(out[f]) for f in TCPRX_OUT_FIELDS})
+    return b, rin, rout
+
+
+def tcp_rx_host(frames, pkt_len, sock, conn, stride=0, offs=None, n=None, frames_len=None, order=None,
+                m=None, l4_status=None, nconn=None, align=0, blocks=0, out=None, counts=None):
+    """gcl_tcp_rx_host: the rule of Classifier.tcp_rx on the CPU over numpy
+    arrays.  @conn is a TCP_CONN_DTYPE array indexed by cookie.  @out maps
+    TCPRX_OUT_FIELDS to arrays (u8, u8, u32, u16, u64, TCP_CONN_OUT_DTYPE,
+    u64[nconn + 1]); the ones left out are allocated.  @counts is a
+    u64[TCPRXC_NR], accumulated.  Returns the dict."""
+    n = len(pkt_len) if n is None else n
+    m = _pay_m(n, m, order)
+    nconn = len(conn) if nconn is None else nconn
+    out = dict(out or {})
+    for f, dt, k in (("verdict", np.uint8, m), ("sflags", np.uint8, m), ("rcv_nxt_after", np.uint32, m),
+                     ("copy_len", np.uint16, m), ("dst_off", np.uint64, m),
+                     ("out_conn", TCP_CONN_OUT_DTYPE, nconn), ("conn_off", np.uint64, nconn + 1)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    b, rin, rout = _tcprx_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status,
+                                  conn, nconn, align, blocks, out, counts)
+    _check(lib.gcl_tcp_rx_host(ctypes.byref(b), ctypes.byref(rin), ctypes.byref(rout), _ptr(counts)),
+           "gcl_tcp_rx_host")
+    return out
+
+
+def tcp_rx_workspace(m, nconn, blocks=0):
+    """gcl_tcp_rx_workspace: bytes of device scratch a call over @m entries and @nconn connections takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_rx_workspace(m, nconn, blocks, ctypes.byref(need)), "gcl_tcp_rx_workspace")
     return need.value
 
 
@@ -1470,6 +1568,44 @@ class Classifier:
                 ws = self._seg_ws = torch.empty(need, dtype=torch.uint8, device=out["total_segs"].device)
         _check(lib.gcl_tx_seg(self._ctx, ctypes.byref(sin), ctypes.byref(sout), _ptr(counts), _ptr(ws),
                               _nbytes(ws), stream), "gcl_tx_seg")
+        return out
+
+    def tcp_rx(self, frames, n, pkt_len, sock, conn, nconn, stride=0, offs=None, frames_len=None,
+               order=None, m=None, l4_status=None, align=0, blocks=0, out=None, counts=None,
+               workspace=None, stream=None):
+        """gcl_tcp_rx: tcp_rx_conn's established fast path for one runtime's
+        list @order[0..m) (None: every packet in turn) on the GPU,
+        asynchronous.  @sock is what sock_lookup wrote, @l4_status what
+        l4_csum(L4_VERIFY) wrote, @conn a device uint8[nconn, 48] holding
+        TCP_CONN_DTYPE records indexed by cookie (16-B aligned).  @out maps
+        TCPRX_OUT_FIELDS to device buffers; the ones left out are allocated on
+        @frames' device (verdict and sflags uint8, rcv_nxt_after int32,
+        copy_len int16, dst_off and conn_off int64, out_conn uint8[nconn, 48]).
+        @counts is a device u64[TCPRXC_NR], accumulated.  The scratch is
+        @workspace, or a torch tensor kept on the classifier.  Returns the
+        dict: with l4_payload's src_off, copy_len and dst_off are copy_batch's
+        length and dst_off."""
+        import torch
+        m = _pay_m(n, m, order)
+        dev = frames.device if hasattr(frames, "device") else None
+        out = dict(out or {})
+        mm = max(m, 1)
+        for f, dt, shape in (("verdict", torch.uint8, (mm,)), ("sflags", torch.uint8, (mm,)),
+                             ("rcv_nxt_after", torch.int32, (mm,)), ("copy_len", torch.int16, (mm,)),
+                             ("dst_off", torch.int64, (mm,)), ("out_conn", torch.uint8, (max(nconn, 1), 48)),
+                             ("conn_off", torch.int64, (nconn + 1,))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        b, rin, rout = _tcprx_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock,
+                                      l4_status, conn, nconn, align, blocks, out, counts)
+        ws = workspace
+        if ws is None:
+            need = tcp_rx_workspace(m, nconn, blocks)
+            ws = getattr(self, "_tcprx_ws", None)
+            if ws is None or ws.numel() < need or ws.device != out["conn_off"].device:
+                ws = self._tcprx_ws = torch.empty(need, dtype=torch.uint8, device=out["conn_off"].device)
+        _check(lib.gcl_tcp_rx(self._ctx, ctypes.byref(b), ctypes.byref(rin), ctypes.byref(rout),
+                              _ptr(counts), _ptr(ws), _nbytes(ws), stream), "gcl_tcp_rx")
         return out
 
     def copy_batch(self, src, src_off, length, n, dst, dst_off=None, dst_stride=0, tx_olflags=None,

@@ -230,6 +230,23 @@ int gcl_tx_hdr_host(const struct gcl_neigh_tbl *tbl, const uint8_t rss_key[40],
 int gcl_tx_seg_host(const struct gcl_seg_in *in, const struct gcl_seg_out *out, uint64_t *counts);
 
 /*
+ * gcl_tcp_rx_host - the rule of gcl_tcp_rx (gclassify.h) on the CPU over host
+ * pointers, for the lists the GPU did not see: tcp_rx_conn's established fast
+ * path (runtime/net/tcp_in.c:197-296) for every connection's segments in
+ * arrival order, sequential plain C with the rule the kernels share
+ * (csrc/gcl_tcprx.h).  It walks the list once and keeps every connection's
+ * live words in out_conn, so it needs no grouping and no workspace; a second
+ * walk adds conn_off to the FAST entries' dst_off.  @b, @in and @out are
+ * gcl_tcp_rx's structs with every pointer a host pointer (in->blocks is
+ * checked against GCL_TCPRX_MAX_BLOCKS and otherwise not looked at); @counts
+ * is a host u64[GCL_TCPRXC_NR], ACCUMULATED, may be NULL.  The same outputs
+ * byte for byte, the same counts and the same guarantee.  0, or -EINVAL for
+ * what gcl_tcp_rx refuses (the ctx and the workspace apart).
+ */
+int gcl_tcp_rx_host(const struct gcl_batch *b, const struct gcl_tcprx_in *in,
+                    const struct gcl_tcprx_out *out, uint64_t *counts);
+
+/*
  * gcl_host_deliver - consume @n verdicts in order.
  * @clients_by_id  dp.clients_by_id (iokernel/defs.h:386), @max_runtimes long
  * @clients        dp.clients[0..nr_clients) (broadcast order, rx.c:175)

@@ -1650,6 +1650,183 @@ int gcl_tx_seg_workspace(uint64_t m, uint32_t blocks, size_t *bytes);
 int gcl_tx_seg(struct gcl_ctx *ctx, const struct gcl_seg_in *in, const struct gcl_seg_out *out,
                uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/*
+ * TCP receive, the established fast path: the step behind gcl_l4_payload for
+ * TCP.  tcp_rx_conn (runtime/net/tcp_in.c:172-296) is written as a fast path:
+ * an established connection, the next in-order segment, one that fits the
+ * receive window, no FIN / RST / URG; everything else leaves through
+ * __tcp_rx_conn.  Under the connection lock it compares seq with rcv_nxt,
+ * moves the windows and counts delayed ACKs, once per segment on a core.
+ * gcl_tcp_rx runs every connection's segments of one runtime's list, in
+ * arrival order, through that fast path on the GPU, and lays the bytes each
+ * connection accepted out contiguously and in sequence order:
+ *
+ *   gcl_classify -> gcl_sock_lookup -> gcl_l4_csum VERIFY -> gcl_plan ->
+ *   gcl_l4_payload -> gcl_tcp_rx -> gcl_copy_batch (src_off from
+ *   gcl_l4_payload; len = copy_len and dst_off from this call).
+ *
+ * A connection stops at its first segment that needs __tcp_rx_conn; the
+ * runtime gets, per connection, the new PCB words, a byte range and the list
+ * position of the first segment it must still look at itself.  One call
+ * serves ONE runtime, because cookies are per runtime (as gcl_tx_hdr serves
+ * one): @in->order / m are that runtime's range of a plan, @in->conn its
+ * connections indexed by cookie.  It works on every context and touches no
+ * table.
+ *
+ * List entry j names packet i = in->order ? in->order[j] : j.  It is a TCP
+ * SEGMENT exactly when gcl_l4_payload, given the same sock and l4_status,
+ * keeps it as GCL_PAY_TCP (the very function decides, gcl_pay_rule), with
+ * c = sock[i] its connection; len is gcl_l4_payload's len, and seq, ack, flags
+ * and win are frame bytes 38-41, 42-45, 47 and 48-49 (a kept TCP entry has
+ * L >= 54).  The verdict of entry j is the first line that matches, the
+ * entries of a connection taken in list order:
+ *   not a TCP segment (OOR, NA, UDP, BADCSUM, NOSOCK)       GCL_TCPRX_NA
+ *   c >= nconn                                               GCL_TCPRX_NOCONN
+ *   len > conn[c].rcv_mss (tcp_in.c:207: freed before the
+ *     lock is taken; it neither reads nor changes state and
+ *     does not stop the connection)                          GCL_TCPRX_DROP
+ *   the connection has stopped earlier in this call, or
+ *     slow_path of :221-239 holds for its current state:
+ *     flags & (FIN | RST | URG), len == 0,
+ *     wraps_gt(ack, snd_nxt), not GCL_TCPC_ELIGIBLE,
+ *     wraps_lte(snd_una + snd_wnd, snd_nxt), seq != rcv_nxt,
+ *     rcv_wnd < len                                          GCL_TCPRX_SLOW
+ *     (the first such segment STOPS the connection: its state
+ *     is frozen as it stood before that segment)
+ *   otherwise                                                GCL_TCPRX_FAST
+ * SYN is not a slow-path flag and the ACK flag is not tested: both as in the
+ * reference.  A FAST segment applies :246-287 to the connection's state:
+ *   if wraps_lte(snd_una, ack):
+ *     if snd_una != ack: snd_una = ack (sflags ACKED; rep_acks = 0)
+ *     if wraps_lt(snd_wl1, seq) or (snd_wl1 == seq and wraps_lte(snd_wl2, ack)):
+ *       snd_wnd = win << snd_wscale, snd_wl1 = seq, snd_wl2 = ack
+ *       (sflags WND; rep_acks = 0)
+ *   rcv_nxt += len, rcv_wnd -= len
+ *   wake (sflags WAKE) when GCL_TCPC_RXQ is set or the segment carries PSH
+ *   if ++acks_delayed_cnt >= 2: do_ack (sflags ACK_NOW), the counter 0 and
+ *     ACK_DELAYED cleared; else if ACK_DELAYED is clear: it is set and the
+ *     timer armed (out flags TIMER_ARMED)
+ *   GCL_TCPC_RXQ is set (the mbuf joined rxq).
+ * All arithmetic is mod 2^32 with the reference's wraps_* comparisons
+ * ((int32_t)(a - b) < 0 and its kin); acks_delayed_cnt is taken as the
+ * reference's int, so a counter of 1 or more on entry gives do_ack.
+ *
+ * Per-entry outputs (m elements each): verdict; sflags; rcv_nxt_after, the
+ * number tcp_tx_ack would carry after a FAST segment, 0 otherwise; copy_len
+ * and dst_off (below).  Per connection, out_conn[c] holds the six words that
+ * move, acks_delayed_cnt and flags as they stand after the list, nfast / nslow
+ * (FAST and SLOW verdicts of the connection) / nacks (ACK_NOW segments), and
+ * first_slow, the list position j of the stopping segment or 0xFFFFFFFF.  A
+ * connection with no segment in the list gets its input back with zero counts.
+ *
+ * The in-order layout, with pad() as in gcl_l4_payload and in->align:
+ *   fast_bytes[c] = out_conn[c].rcv_nxt - conn[c].rcv_nxt (mod 2^32)
+ *   conn_off[c]   = the sum of pad(fast_bytes[c']) over c' < c, c <= nconn:
+ *                   conn_off[nconn] is the total
+ *   a FAST entry:  copy_len = len, dst_off = conn_off[c] + (seq - conn[c].rcv_nxt)
+ *   every other:   copy_len = 0,   dst_off = 0.
+ * gcl_copy_batch with these then leaves connection c's accepted bytes at
+ * [conn_off[c], conn_off[c] + fast_bytes[c]) in sequence order; the SLOW
+ * entries stay reachable through gcl_l4_payload's own layout.
+ *
+ * Every pointer is a device pointer; each array is aligned to its element,
+ * conn and out_conn to 16 B.  @counts is a device u64[GCL_TCPRXC_NR],
+ * ACCUMULATED, may be NULL: FAST, SLOW, DROP, NOCONN and NA entries (per call
+ * the five sum to m), BYTES (the sum of copy_len), ACKS (ACK_NOW) and WAKES.
+ * Frames are addressed as gcl_l4_payload addresses them.
+ *
+ * Guarantee: no content of frames, offs, pkt_len, order, sock, l4_status or
+ * conn causes a read outside frames[0, frames_len) or the given arrays
+ * (order[0, m), the n-element per-packet arrays, conn[0, nconn)), or a write
+ * outside the m-element outputs, out_conn[0, nconn), conn_off[0, nconn],
+ * counts and the workspace.
+ *
+ * What stays with the runtime: all of __tcp_rx_conn (every SLOW segment and
+ * what follows it on its connection), the out-of-order queue, tcp_conn_ack's
+ * mbuf frees (ACKED says when), the wake-ups (WAKE), sending the ACKs
+ * (ACK_NOW, with rcv_nxt_after), ack_ts and next_timeout (TIMER_ARMED), the
+ * timers, and the lock: conn must be a snapshot no core changes meanwhile.
+ *
+ * gcl_tcp_rx_workspace - bytes of device scratch a call takes for m entries,
+ *   nconn connections and in->blocks = @blocks.  -EINVAL for a NULL @bytes,
+ *   m > 2^31, nconn > 2^20 or blocks > GCL_TCPRX_MAX_BLOCKS.
+ * gcl_tcp_rx - asynchronous on @hip_stream: launches ordered by the stream
+ *   alone; no block waits for another and no atomic's order decides a result.
+ *   No allocation, no host synchronisation.  @workspace (device, 16-B aligned)
+ *   need not be zeroed and may be reused by the next call on the same stream.
+ *   m == 0 still writes out_conn and conn_off.  -EINVAL for a NULL ctx, b, in
+ *   or out; a wrong in->size; a bad align; order == NULL with m != b->n;
+ *   m > 2^31; nconn > 2^20; a NULL sock; with nconn > 0 a NULL conn or
+ *   out_conn; a NULL conn_off; with m > 0 a NULL verdict, sflags,
+ *   rcv_nxt_after, copy_len or dst_off; any given array that is not aligned to
+ *   its element (conn, out_conn: 16 B); blocks > GCL_TCPRX_MAX_BLOCKS; a NULL
+ *   workspace, one that is not 16-B aligned or one smaller than
+ *   gcl_tcp_rx_workspace says; and, when m > 0, what gcl_l4_payload refuses of
+ *   a batch.  -EIO when a launch fails.
+ */
+/* verdict[j], and the first five counter slots */
+#define GCL_TCPRX_FAST   0
+#define GCL_TCPRX_SLOW   1
+#define GCL_TCPRX_DROP   2
+#define GCL_TCPRX_NOCONN 3
+#define GCL_TCPRX_NA     4
+#define GCL_TCPRX_MAX_BLOCKS 1024  /* the cap on in->blocks */
+#define GCL_TCPRX_MAX_CONN (1u << 20)
+enum { GCL_TCPRXC_FAST = 0, GCL_TCPRXC_SLOW, GCL_TCPRXC_DROP, GCL_TCPRXC_NOCONN, GCL_TCPRXC_NA,
+       GCL_TCPRXC_BYTES, GCL_TCPRXC_ACKS, GCL_TCPRXC_WAKES, GCL_TCPRXC_NR = 8 };
+/* sflags[j] */
+#define GCL_TCPRX_SF_WAKE    0x01  /* waitq_signal + POLLIN */
+#define GCL_TCPRX_SF_ACK_NOW 0x02  /* do_ack: tcp_tx_ack with rcv_nxt_after[j] */
+#define GCL_TCPRX_SF_ACKED   0x04  /* snd_una moved: run tcp_conn_ack */
+#define GCL_TCPRX_SF_WND     0x08  /* snd_wnd, snd_wl1 and snd_wl2 were rewritten */
+/* gcl_tcp_conn.flags */
+#define GCL_TCPC_ELIGIBLE    0x01  /* state == ESTABLISHED && list_empty(&rxq_ooo) */
+#define GCL_TCPC_RXQ         0x02  /* !list_empty(&rxq) */
+#define GCL_TCPC_ACK_DELAYED 0x04  /* c->ack_delayed */
+/* gcl_tcp_conn_out.flags: RXQ and ACK_DELAYED as above, and */
+#define GCL_TCPO_STOPPED        0x08  /* first_slow is valid */
+#define GCL_TCPO_WOKEN          0x10  /* some segment had WAKE */
+#define GCL_TCPO_TIMER_ARMED    0x20  /* set ack_ts = microtime(), lower next_timeout */
+#define GCL_TCPO_REP_ACKS_RESET 0x40  /* rep_acks = 0 */
+struct gcl_tcp_conn {      /* 48 B, 16-B aligned, host order: the PCB words the fast path reads */
+	uint32_t snd_una, snd_nxt, snd_wnd, snd_wl1, snd_wl2, rcv_nxt, rcv_wnd;
+	uint16_t rcv_mss;
+	uint8_t  snd_wscale;   /* the low five bits are used: a shift of 0..31 */
+	uint8_t  flags;        /* GCL_TCPC_* */
+	uint8_t  acks_delayed_cnt, pad[15];
+};
+struct gcl_tcp_conn_out {  /* 48 B, 16-B aligned */
+	uint32_t snd_una, snd_wnd, snd_wl1, snd_wl2, rcv_nxt, rcv_wnd;
+	uint32_t nfast, nslow, nacks;
+	uint32_t first_slow;   /* list position, or 0xFFFFFFFF */
+	uint8_t  acks_delayed_cnt;
+	uint8_t  flags;        /* GCL_TCPC_RXQ, GCL_TCPC_ACK_DELAYED, GCL_TCPO_* */
+	uint8_t  pad[6];
+};
+struct gcl_tcprx_in {
+	uint32_t size, align;            /* sizeof(struct gcl_tcprx_in); align as in gcl_pay_in */
+	const uint32_t *order;           /* optional u32[m]; NULL: m == b->n and i = j */
+	uint64_t m;                      /* list entries, <= 2^31 */
+	const uint32_t *sock;            /* REQUIRED u32[n], as gcl_sock_lookup wrote it */
+	const uint8_t  *l4_status;       /* optional u8[n], as GCL_L4_VERIFY wrote it */
+	const struct gcl_tcp_conn *conn; /* [nconn], indexed by cookie */
+	uint32_t nconn;                  /* <= 2^20 */
+	uint32_t blocks;                 /* 0: the library's choice; else the number of contiguous
+	                                    list ranges the grouping is cut into (tests) */
+};
+struct gcl_tcprx_out {               /* device, aligned to their element */
+	uint8_t  *verdict, *sflags;      /* [m] */
+	uint32_t *rcv_nxt_after;         /* [m] */
+	uint16_t *copy_len;              /* [m] */
+	uint64_t *dst_off;               /* [m] */
+	struct gcl_tcp_conn_out *out_conn; /* [nconn] */
+	uint64_t *conn_off;              /* u64[nconn + 1] */
+};
+int gcl_tcp_rx_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, size_t *bytes);
+int gcl_tcp_rx(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct gcl_tcprx_in *in,
+               const struct gcl_tcprx_out *out, uint64_t *counts,
+               void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
