@@ -11,6 +11,7 @@
 #include "gcl_pay.h"
 #include "gcl_seg.h"
 #include "gcl_tcprx.h"
+#include "gcl_tcptmr.h"
 #include "gcl_txh.h"
 
 #define ROT(x, k) (((x) << (k)) | ((x) >> (32 - (k))))
@@ -702,6 +703,122 @@ int gcl_tcp_rx_host(const struct gcl_batch *b, const struct gcl_tcprx_in *in,
 	if (counts)
 		for (int k = 0; k < GCL_TCPRXC_NR; k++)
 			counts[k] += c[k];
+	return 0;
+}
+
+/* what gcl_tcp_tick and gcl_tcp_rx_acks both refuse of the fields they share */
+static int ctl_refused(uint32_t nconn, uint32_t blocks, uint64_t seg_cap, uint32_t frame_stride, uint64_t items,
+                       const struct gcl_ctlseg_out *o, const uint64_t *counts)
+{
+	if (nconn > GCL_TICK_MAX_CONN || blocks > GCL_TICK_MAX_BLOCKS || seg_cap > (1ull << 31) ||
+	    frame_stride < GCL_CTL_MIN_STRIDE || !o->totals)
+		return 1;
+	if (items && seg_cap && (!o->desc || !o->frame_off || !o->seg_conn || !o->seg_kind || !o->seg_src))
+		return 1;
+	return ((uintptr_t)o->desc & 15) || ((uintptr_t)o->frame_off & 7) || ((uintptr_t)o->seg_conn & 3) ||
+	       ((uintptr_t)o->seg_src & 3) || ((uintptr_t)o->totals & 7) || ((uintptr_t)counts & 7);
+}
+
+/* segment @at of a call, when it lies below @seg_cap; returns whether it was written */
+static int ctl_emit(const struct gcl_ctlseg_out *o, uint64_t at, uint64_t seg_cap, uint64_t frame_base,
+                    uint32_t frame_stride, const struct gcl_tcp_conn *cn, const struct gcl_tcp_addr *ad, uint32_t c,
+                    uint32_t kind, uint32_t src, uint32_t ack, uint32_t rcv_wnd)
+{
+	uint32_t a[4], d[8];
+
+	if (at >= seg_cap)
+		return 0;
+	memcpy(a, ad, sizeof(a)); /* little-endian host */
+	gcl_ctl_desc(a, gcl_ctl_seq(kind, cn->snd_una, cn->snd_nxt), ack, rcv_wnd, d);
+	memcpy(&o->desc[at], d, sizeof(o->desc[at]));
+	o->frame_off[at] = frame_base + at * frame_stride;
+	o->seg_conn[at] = c;
+	o->seg_kind[at] = (uint8_t)kind;
+	o->seg_src[at] = src;
+	return 1;
+}
+
+/* The rule of gcl_tcp_tick (gclassify.h) on the CPU: gcl_tmr_sweep of
+ * gcl_tcptmr.h for every connection in turn, the segment count running. */
+int gcl_tcp_tick_host(const struct gcl_tick_in *in, const struct gcl_tick_out *out, uint64_t *counts)
+{
+	uint64_t c[GCL_TICKC_NR] = {0}, at = 0;
+
+	if (!in || !out || in->size != sizeof(*in) ||
+	    ctl_refused(in->nconn, in->blocks, in->seg_cap, in->frame_stride, in->nconn, &out->seg, counts))
+		return -EINVAL;
+	if (in->nconn && (!in->tmr || !in->conn || !in->addr || !out->out_tmr))
+		return -EINVAL;
+	if (((uintptr_t)in->tmr & 15) || ((uintptr_t)in->conn & 15) || ((uintptr_t)in->addr & 15) ||
+	    ((uintptr_t)out->out_tmr & 15))
+		return -EINVAL;
+	for (uint32_t k = 0; k < in->nconn; k++) {
+		struct gcl_tcp_tmr_out o;
+		uint32_t action = gcl_tmr_sweep(&in->tmr[k], in->now, &o);
+		const uint32_t sg = gcl_tmr_segs(action);
+		const struct gcl_tcp_conn *cn = &in->conn[k];
+		int lost = 0;
+
+		for (uint32_t kind = GCL_CTL_ACK; kind <= GCL_CTL_PROBE; kind++)
+			if (sg & (1u << kind)) {
+				lost |= !ctl_emit(&out->seg, at, in->seg_cap, in->frame_base, in->frame_stride, cn,
+				                  &in->addr[k], k, kind, k, cn->rcv_nxt, cn->rcv_wnd);
+				at++;
+			}
+		if (lost) {
+			action |= GCL_TMRA_NOSPACE;
+			o.action = (uint8_t)action;
+		}
+		out->out_tmr[k] = o;
+		for (int x = 0; x <= GCL_TICKC_NOSPACE; x++)
+			c[x] += (action >> x) & 1u;
+	}
+	out->seg.totals[0] = at;
+	out->seg.totals[1] = c[GCL_TICKC_SEGS] = at < in->seg_cap ? at : in->seg_cap;
+	if (counts)
+		for (int k = 0; k < GCL_TICKC_NR; k++)
+			counts[k] += c[k];
+	return 0;
+}
+
+/* The rule of gcl_tcp_rx_acks (gclassify.h) on the CPU: one walk over the list. */
+int gcl_tcp_rx_acks_host(const struct gcl_rxack_in *in, const struct gcl_ctlseg_out *out, uint64_t *counts)
+{
+	uint64_t at = 0, skipped = 0;
+
+	if (!in || !out || in->size != sizeof(*in) || in->m > (1ull << 31) ||
+	    ctl_refused(in->nconn, in->blocks, in->seg_cap, in->frame_stride, in->m, out, counts))
+		return -EINVAL;
+	if (in->m && (!in->sock || !in->verdict || !in->sflags || !in->rcv_nxt_after))
+		return -EINVAL;
+	if (in->m && in->nconn && (!in->conn || !in->addr))
+		return -EINVAL;
+	if (((uintptr_t)in->order & 3) || ((uintptr_t)in->sock & 3) || ((uintptr_t)in->rcv_nxt_after & 3) ||
+	    ((uintptr_t)in->conn & 15) || ((uintptr_t)in->addr & 15))
+		return -EINVAL;
+	for (uint64_t j = 0; j < in->m; j++) {
+		if (!gcl_rxack_asked(in->verdict[j], in->sflags[j]))
+			continue;
+		const uint64_t i = in->order ? in->order[j] : j;
+		const uint32_t k = i < in->n ? in->sock[i] : UINT32_MAX;
+
+		if (k >= in->nconn) {
+			skipped++;
+			continue;
+		}
+		const struct gcl_tcp_conn *cn = &in->conn[k];
+		const uint32_t after = in->rcv_nxt_after[j];
+		(void)ctl_emit(out, at, in->seg_cap, in->frame_base, in->frame_stride, cn, &in->addr[k], k, GCL_CTL_ACK,
+		               (uint32_t)j, after, gcl_rxack_wnd(cn->rcv_wnd, cn->rcv_nxt, after));
+		at++;
+	}
+	out->totals[0] = at;
+	out->totals[1] = at < in->seg_cap ? at : in->seg_cap;
+	if (counts) {
+		counts[GCL_RXACKC_WANTED] += at;
+		counts[GCL_RXACKC_WRITTEN] += out->totals[1];
+		counts[GCL_RXACKC_SKIPPED] += skipped;
+	}
 	return 0;
 }
 

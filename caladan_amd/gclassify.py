@@ -119,6 +119,27 @@ TCP_CONN_OUT_DTYPE = np.dtype([("snd_una", "<u4"), ("snd_wnd", "<u4"), ("snd_wl1
                                ("rcv_nxt", "<u4"), ("rcv_wnd", "<u4"), ("nfast", "<u4"), ("nslow", "<u4"),
                                ("nacks", "<u4"), ("first_slow", "<u4"), ("acks_delayed_cnt", "u1"),
                                ("flags", "u1"), ("pad", "u1", (6,))])
+# gcl_tcp_tick / gcl_tcp_rx_acks: the timer flags, the action bits (bits 0..6 are also the first
+# counter slots), the segment kinds, the counters, the caps, the TCP states the sweep tests,
+# struct gcl_tcp_tmr, struct gcl_tcp_tmr_out and struct gcl_tcp_addr
+TMR_LIVE, TMR_ACK_DELAYED, TMR_ZERO_WND, TMR_TX_EXCLUSIVE, TMR_TXQ, TMR_OOO = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+(TMRA_FIRED, TMRA_ACK, TMRA_PROBE, TMRA_RETRANSMIT, TMRA_FAIL, TMRA_CLOSE,
+ TMRA_NOSPACE) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
+CTL_ACK, CTL_PROBE, CTL_MIN_STRIDE = 0, 1, 54
+(TICKC_FIRED, TICKC_ACK, TICKC_PROBE, TICKC_RETRANSMIT, TICKC_FAIL, TICKC_CLOSE, TICKC_NOSPACE,
+ TICKC_SEGS) = range(8)
+TICKC_NR, TICK_MAX_BLOCKS, TICK_MAX_CONN = 8, 1024, 1 << 20
+RXACKC_WANTED, RXACKC_WRITTEN, RXACKC_SKIPPED = range(3)
+TCP_STATE_ESTABLISHED, TCP_STATE_TIME_WAIT, TCP_STATE_CLOSED = 2, 8, 9
+# its launches (csrc/gcl_tcptmr.hip): connections or list entries per tile
+TICK_TILE = 256
+TCP_TMR_DTYPE = np.dtype([("next_timeout", "<u8"), ("attach_ts", "<u8"), ("time_wait_ts", "<u8"),
+                          ("ack_ts", "<u8"), ("zero_wnd_ts", "<u8"), ("txq_ts", "<u8"), ("state", "u1"),
+                          ("flags", "u1"), ("pad", "u1", (14,))])
+TCP_TMR_OUT_DTYPE = np.dtype([("next_timeout", "<u8"), ("zero_wnd_ts", "<u8"), ("state", "u1"), ("flags", "u1"),
+                              ("action", "u1"), ("pad", "u1", (13,))])
+TCP_ADDR_DTYPE = np.dtype([("lip", "<u4"), ("rip", "<u4"), ("lport", "<u2"), ("rport", "<u2"),
+                           ("rcv_wscale", "u1"), ("pad", "u1", (3,))])
 STAT_NAMES = ["RX_UNREGISTERED_MAC", "RX_UNICAST_FAIL", "RX_BROADCAST_FAIL",
               "RX_FLOW_TAG_MATCH", "RX_UNHANDLED", "RX_HASH_MISSING", "RX_PULLED"]
 
@@ -371,6 +392,37 @@ class GclTcprxOut(ctypes.Structure):
     _fields_ = [(f, ctypes.c_void_p) for f in TCPRX_OUT_FIELDS]
 
 
+CTLSEG_SEG_FIELDS = ("desc", "frame_off", "seg_conn", "seg_kind", "seg_src")
+CTLSEG_OUT_FIELDS = CTLSEG_SEG_FIELDS + ("totals",)
+TICK_OUT_FIELDS = ("out_tmr",) + CTLSEG_OUT_FIELDS
+
+
+class GclCtlsegOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in CTLSEG_OUT_FIELDS]
+
+
+class GclTickIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("now", ctypes.c_uint64),
+                ("tmr", ctypes.c_void_p), ("conn", ctypes.c_void_p), ("addr", ctypes.c_void_p),
+                ("nconn", ctypes.c_uint32), ("frame_stride", ctypes.c_uint32), ("seg_cap", ctypes.c_uint64),
+                ("frame_base", ctypes.c_uint64)]
+
+
+class GclTickOut(ctypes.Structure):
+    _fields_ = [("out_tmr", ctypes.c_void_p), ("seg", GclCtlsegOut)]
+
+
+class GclRxackIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("order", ctypes.c_void_p),
+                ("m", ctypes.c_uint64), ("n", ctypes.c_uint64), ("sock", ctypes.c_void_p),
+                ("verdict", ctypes.c_void_p), ("sflags", ctypes.c_void_p), ("rcv_nxt_after", ctypes.c_void_p),
+                ("conn", ctypes.c_void_p), ("addr", ctypes.c_void_p), ("nconn", ctypes.c_uint32),
+                ("frame_stride", ctypes.c_uint32), ("seg_cap", ctypes.c_uint64), ("frame_base", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(GclTickIn) == 64 and ctypes.sizeof(GclTickOut) == 56 and ctypes.sizeof(GclRxackIn) == 104
+assert ctypes.sizeof(GclCtlsegOut) == 48 and TCP_TMR_DTYPE.itemsize == 64 and TCP_TMR_OUT_DTYPE.itemsize == 32
+assert TCP_ADDR_DTYPE.itemsize == 16
 assert ctypes.sizeof(GclTcprxIn) == 56 and ctypes.sizeof(GclTcprxOut) == 56
 assert TCP_CONN_DTYPE.itemsize == 48 and TCP_CONN_OUT_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclSegIn) == 64 and ctypes.sizeof(GclSegOut) == 104 and SEG_SEND_DTYPE.itemsize == 48
@@ -478,6 +530,14 @@ def _load():
                              ctypes.POINTER(GclTcprxOut), vp, vp, ctypes.c_size_t, vp]),
         "gcl_tcp_rx_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxIn),
                                   ctypes.POINTER(GclTcprxOut), vp]),
+        "gcl_tcp_tick_workspace": (i32, [u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_tick": (i32, [vp, ctypes.POINTER(GclTickIn), ctypes.POINTER(GclTickOut), vp, vp,
+                               ctypes.c_size_t, vp]),
+        "gcl_tcp_tick_host": (i32, [ctypes.POINTER(GclTickIn), ctypes.POINTER(GclTickOut), vp]),
+        "gcl_tcp_rx_acks_workspace": (i32, [u64, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_rx_acks": (i32, [vp, ctypes.POINTER(GclRxackIn), ctypes.POINTER(GclCtlsegOut), vp, vp,
+                                  ctypes.c_size_t, vp]),
+        "gcl_tcp_rx_acks_host": (i32, [ctypes.POINTER(GclRxackIn), ctypes.POINTER(GclCtlsegOut), vp]),
         "gcl_neigh_tbl_new": (vp, []),
         "gcl_neigh_tbl_free": (None, [vp]),
         "gcl_neigh_tbl_set": (i32, [vp, vp, u32]),
@@ -1020,6 +1080,112 @@ def tcp_rx_workspace(m, nconn, blocks=0):
     """gcl_tcp_rx_workspace: bytes of device scratch a call over @m entries and @nconn connections takes."""
     need = ctypes.c_size_t()
     _check(lib.gcl_tcp_rx_workspace(m, nconn, blocks, ctypes.byref(need)), "gcl_tcp_rx_workspace")
+    return need.value
+
+
+CTLSEG_OUT_WIDTH = {"desc": 32, "frame_off": 8, "seg_conn": 4, "seg_kind": 1, "seg_src": 4}
+
+
+def _ctlseg_struct(seg_cap, out, counts):
+    """struct gcl_ctlseg_out of @out (CTLSEG_OUT_FIELDS to buffers), sizes checked"""
+    for f in CTLSEG_SEG_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < CTLSEG_OUT_WIDTH[f] * seg_cap:
+            raise ValueError(f"{f}: per-segment array shorter than seg_cap")
+    if out["totals"] is not None and _nbytes(out["totals"]) < 16:
+        raise ValueError("totals too small")
+    if counts is not None and _nbytes(counts) < 8 * TICKC_NR:
+        raise ValueError("counts buffer too small")
+    return GclCtlsegOut(**{f: _ptr(out[f]) for f in CTLSEG_OUT_FIELDS})
+
+
+def _tick_structs(now, tmr, conn, addr, nconn, seg_cap, frame_base, frame_stride, blocks, out, counts):
+    """The two structs of gcl_tcp_tick / gcl_tcp_tick_host, sizes checked; @out
+    maps TICK_OUT_FIELDS to buffers."""
+    for arr, w in ((tmr, 64), (conn, 48), (addr, 16), (out["out_tmr"], 32)):
+        if arr is not None and _nbytes(arr) < w * nconn:
+            raise ValueError("per-connection array too small")
+    tin = GclTickIn(size=ctypes.sizeof(GclTickIn), blocks=blocks, now=now, tmr=_ptr(tmr), conn=_ptr(conn),
+                    addr=_ptr(addr), nconn=nconn, frame_stride=frame_stride, seg_cap=seg_cap,
+                    frame_base=frame_base)
+    tout = GclTickOut(out_tmr=_ptr(out["out_tmr"]), seg=_ctlseg_struct(seg_cap, out, counts))
+    return tin, tout
+
+
+def _rxack_structs(verdict, sflags, rcv_nxt_after, sock, conn, addr, m, n, nconn, order, seg_cap, frame_base,
+                   frame_stride, blocks, out, counts):
+    """The two structs of gcl_tcp_rx_acks / gcl_tcp_rx_acks_host, sizes checked;
+    @out maps CTLSEG_OUT_FIELDS to buffers."""
+    for arr, w in ((order, 4), (verdict, 1), (sflags, 1), (rcv_nxt_after, 4)):
+        if arr is not None and _nbytes(arr) < w * m:
+            raise ValueError("per-entry array too small")
+    if sock is not None and _nbytes(sock) < 4 * n:
+        raise ValueError("sock too small")
+    for arr, w in ((conn, 48), (addr, 16)):
+        if arr is not None and _nbytes(arr) < w * nconn:
+            raise ValueError("per-connection array too small")
+    rin = GclRxackIn(size=ctypes.sizeof(GclRxackIn), blocks=blocks, order=_ptr(order), m=m, n=n, sock=_ptr(sock),
+                     verdict=_ptr(verdict), sflags=_ptr(sflags), rcv_nxt_after=_ptr(rcv_nxt_after),
+                     conn=_ptr(conn), addr=_ptr(addr), nconn=nconn, frame_stride=frame_stride, seg_cap=seg_cap,
+                     frame_base=frame_base)
+    return rin, _ctlseg_struct(seg_cap, out, counts)
+
+
+def _ctlseg_host_arrays(out, seg_cap):
+    for f, dt in (("desc", TXH_DESC_DTYPE), ("frame_off", np.uint64), ("seg_conn", np.uint32),
+                  ("seg_kind", np.uint8), ("seg_src", np.uint32)):
+        if f not in out:
+            out[f] = np.zeros(max(seg_cap, 1), dtype=dt)
+    if "totals" not in out:
+        out["totals"] = np.zeros(2, dtype=np.uint64)
+
+
+def tcp_tick_host(now, tmr, conn, addr, seg_cap, frame_stride=64, frame_base=0, nconn=None, blocks=0, out=None,
+                  counts=None):
+    """gcl_tcp_tick_host: the rule of Classifier.tcp_tick on the CPU over
+    numpy arrays.  @tmr, @conn and @addr are TCP_TMR_DTYPE, TCP_CONN_DTYPE and
+    TCP_ADDR_DTYPE arrays indexed by cookie.  @out maps TICK_OUT_FIELDS to
+    arrays (TCP_TMR_OUT_DTYPE[nconn]; per segment TXH_DESC_DTYPE, u64, u32, u8,
+    u32, each @seg_cap long; totals u64[2]); the ones left out are allocated.
+    @counts is a u64[TICKC_NR], accumulated.  Returns the dict."""
+    nconn = len(tmr) if nconn is None else nconn
+    out = dict(out or {})
+    if "out_tmr" not in out:
+        out["out_tmr"] = np.zeros(max(nconn, 1), dtype=TCP_TMR_OUT_DTYPE)
+    _ctlseg_host_arrays(out, seg_cap)
+    tin, tout = _tick_structs(now, tmr, conn, addr, nconn, seg_cap, frame_base, frame_stride, blocks, out, counts)
+    _check(lib.gcl_tcp_tick_host(ctypes.byref(tin), ctypes.byref(tout), _ptr(counts)), "gcl_tcp_tick_host")
+    return out
+
+
+def tcp_rx_acks_host(verdict, sflags, rcv_nxt_after, sock, conn, addr, seg_cap, frame_stride=64, frame_base=0,
+                     order=None, m=None, n=None, nconn=None, blocks=0, out=None, counts=None):
+    """gcl_tcp_rx_acks_host: the rule of Classifier.tcp_rx_acks on the CPU over
+    numpy arrays: @verdict, @sflags and @rcv_nxt_after as tcp_rx_host wrote
+    them, @sock, @order, @conn as it was given them.  @out maps
+    CTLSEG_OUT_FIELDS to arrays; the ones left out are allocated.  @counts is a
+    u64[TICKC_NR], accumulated (RXACKC_* slots).  Returns the dict."""
+    m = len(verdict) if m is None else m
+    n = len(sock) if n is None else n
+    nconn = len(conn) if nconn is None else nconn
+    out = dict(out or {})
+    _ctlseg_host_arrays(out, seg_cap)
+    rin, rout = _rxack_structs(verdict, sflags, rcv_nxt_after, sock, conn, addr, m, n, nconn, order, seg_cap,
+                               frame_base, frame_stride, blocks, out, counts)
+    _check(lib.gcl_tcp_rx_acks_host(ctypes.byref(rin), ctypes.byref(rout), _ptr(counts)), "gcl_tcp_rx_acks_host")
+    return out
+
+
+def tcp_tick_workspace(nconn, blocks=0):
+    """gcl_tcp_tick_workspace: bytes of device scratch a sweep of @nconn connections takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_tick_workspace(nconn, blocks, ctypes.byref(need)), "gcl_tcp_tick_workspace")
+    return need.value
+
+
+def tcp_rx_acks_workspace(m, blocks=0):
+    """gcl_tcp_rx_acks_workspace: bytes of device scratch a call over @m list entries takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_rx_acks_workspace(m, blocks, ctypes.byref(need)), "gcl_tcp_rx_acks_workspace")
     return need.value
 
 
@@ -1606,6 +1772,73 @@ class Classifier:
                 ws = self._tcprx_ws = torch.empty(need, dtype=torch.uint8, device=out["conn_off"].device)
         _check(lib.gcl_tcp_rx(self._ctx, ctypes.byref(b), ctypes.byref(rin), ctypes.byref(rout),
                               _ptr(counts), _ptr(ws), _nbytes(ws), stream), "gcl_tcp_rx")
+        return out
+
+    def _ctlseg_device_arrays(self, out, seg_cap, dev):
+        import torch
+        cc = max(seg_cap, 1)
+        for f, dt, shape in (("desc", torch.uint8, (cc, 32)), ("frame_off", torch.int64, (cc,)),
+                             ("seg_conn", torch.int32, (cc,)), ("seg_kind", torch.uint8, (cc,)),
+                             ("seg_src", torch.int32, (cc,)), ("totals", torch.int64, (2,))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+
+    def _tick_ws(self, need, dev):
+        import torch
+        ws = getattr(self, "_tick_ws_buf", None)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = self._tick_ws_buf = torch.empty(need, dtype=torch.uint8, device=dev)
+        return ws
+
+    def tcp_tick(self, now, tmr, conn, addr, nconn, seg_cap, frame_stride=64, frame_base=0, blocks=0,
+                 out=None, counts=None, workspace=None, stream=None):
+        """gcl_tcp_tick: the TCP timer sweep of one runtime's @nconn
+        connections at the clock reading @now (us) on the GPU, asynchronous:
+        tcp_worker's loop with tcp_handle_timeouts and tcp_timer_update, and
+        the ACK and window-probe segments it sends.  @tmr, @conn and @addr are
+        device uint8[nconn, 64 / 48 / 16] holding TCP_TMR_DTYPE, TCP_CONN_DTYPE
+        and TCP_ADDR_DTYPE records indexed by cookie (16-B aligned).  @out maps
+        TICK_OUT_FIELDS to device buffers; the ones left out are allocated on
+        @tmr's device (out_tmr uint8[nconn, 32]; desc uint8[seg_cap, 32],
+        frame_off int64, seg_conn and seg_src int32, seg_kind uint8; totals
+        int64[2]).  @counts is a device u64[TICKC_NR], accumulated.  The
+        scratch is @workspace, or a torch tensor kept on the classifier.
+        Returns the dict: desc and frame_off are tx_hdr's, totals[1] its m."""
+        import torch
+        dev = tmr.device if hasattr(tmr, "device") else None
+        out = dict(out or {})
+        if "out_tmr" not in out:
+            out["out_tmr"] = torch.empty((max(nconn, 1), 32), dtype=torch.uint8, device=dev)
+        self._ctlseg_device_arrays(out, seg_cap, dev)
+        tin, tout = _tick_structs(now, tmr, conn, addr, nconn, seg_cap, frame_base, frame_stride, blocks, out,
+                                  counts)
+        ws = workspace if workspace is not None else self._tick_ws(tcp_tick_workspace(nconn, blocks),
+                                                                   out["totals"].device)
+        _check(lib.gcl_tcp_tick(self._ctx, ctypes.byref(tin), ctypes.byref(tout), _ptr(counts), _ptr(ws),
+                                _nbytes(ws), stream), "gcl_tcp_tick")
+        return out
+
+    def tcp_rx_acks(self, verdict, sflags, rcv_nxt_after, m, sock, n, conn, addr, nconn, seg_cap, order=None,
+                    frame_stride=64, frame_base=0, blocks=0, out=None, counts=None, workspace=None,
+                    stream=None):
+        """gcl_tcp_rx_acks: the ACK segments of one tcp_rx call on the GPU,
+        asynchronous: one per FAST entry with TCPRX_SF_ACK_NOW, in list order.
+        @verdict, @sflags and @rcv_nxt_after are tcp_rx's outputs, @sock,
+        @order, @conn and @nconn what it was given; @addr is a device
+        uint8[nconn, 16] of TCP_ADDR_DTYPE records.  @out maps
+        CTLSEG_OUT_FIELDS to device buffers; the ones left out are allocated on
+        @verdict's device.  @counts is a device u64[TICKC_NR], accumulated
+        (RXACKC_* slots).  Returns the dict: desc and frame_off are tx_hdr's,
+        totals[1] its m, seg_src the list position of each ACK."""
+        dev = verdict.device if hasattr(verdict, "device") else None
+        out = dict(out or {})
+        self._ctlseg_device_arrays(out, seg_cap, dev)
+        rin, rout = _rxack_structs(verdict, sflags, rcv_nxt_after, sock, conn, addr, m, n, nconn, order, seg_cap,
+                                   frame_base, frame_stride, blocks, out, counts)
+        ws = workspace if workspace is not None else self._tick_ws(tcp_rx_acks_workspace(m, blocks),
+                                                                   out["totals"].device)
+        _check(lib.gcl_tcp_rx_acks(self._ctx, ctypes.byref(rin), ctypes.byref(rout), _ptr(counts), _ptr(ws),
+                                   _nbytes(ws), stream), "gcl_tcp_rx_acks")
         return out
 
     def copy_batch(self, src, src_off, length, n, dst, dst_off=None, dst_stride=0, tx_olflags=None,

@@ -247,6 +247,23 @@ int gcl_tcp_rx_host(const struct gcl_batch *b, const struct gcl_tcprx_in *in,
                     const struct gcl_tcprx_out *out, uint64_t *counts);
 
 /*
+ * gcl_tcp_tick_host, gcl_tcp_rx_acks_host - the rules of gcl_tcp_tick and
+ * gcl_tcp_rx_acks (gclassify.h) on the CPU over host pointers, for the sweeps
+ * and lists the GPU did not see: tcp_worker's walk with tcp_handle_timeouts and
+ * tcp_timer_update (runtime/net/tcp.c:46-174) at one clock reading, and the
+ * segments of tcp_tx_ack and tcp_tx_probe_window (runtime/net/tcp_out.c:
+ * 178-228), sequential plain C with the rules the kernels share
+ * (csrc/gcl_tcptmr.h) and no workspace.  @in and @out are the calls' structs
+ * with every pointer a host pointer (in->blocks is checked against
+ * GCL_TICK_MAX_BLOCKS and otherwise not looked at); @counts is a host
+ * u64[GCL_TICKC_NR], ACCUMULATED, may be NULL.  The same outputs byte for
+ * byte, the same counts and the same guarantee.  0, or -EINVAL for what the
+ * calls refuse (the ctx and the workspace apart).
+ */
+int gcl_tcp_tick_host(const struct gcl_tick_in *in, const struct gcl_tick_out *out, uint64_t *counts);
+int gcl_tcp_rx_acks_host(const struct gcl_rxack_in *in, const struct gcl_ctlseg_out *out, uint64_t *counts);
+
+/*
  * gcl_host_deliver - consume @n verdicts in order.
  * @clients_by_id  dp.clients_by_id (iokernel/defs.h:386), @max_runtimes long
  * @clients        dp.clients[0..nr_clients) (broadcast order, rx.c:175)

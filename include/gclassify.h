@@ -1827,6 +1827,213 @@ int gcl_tcp_rx(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct gcl_
                const struct gcl_tcprx_out *out, uint64_t *counts,
                void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/*
+ * TCP control segments: the timer sweep, and the ACKs of a gcl_tcp_rx call.
+ * Both chains end where TCP asks for a segment that carries no data.  In the
+ * reference that is per-connection work on a core: tcp_worker
+ * (runtime/net/tcp.c:143-174) wakes every 10 ms, walks the list of all
+ * connections under tcp_lock and runs tcp_handle_timeouts (tcp.c:80-140) and
+ * tcp_timer_update (tcp.c:46-77) on every one whose next_timeout has passed,
+ * which ends in tcp_tx_ack or tcp_tx_probe_window (tcp_out.c:178-228); and
+ * tcp_rx_conn sends one ACK after every do_ack of its fast path
+ * (tcp_in.c:289-290).  gcl_tcp_tick is the sweep of all connections of one
+ * runtime at one clock reading, gcl_tcp_rx_acks the ACKs of one gcl_tcp_rx
+ * call; both write gcl_txh_desc records in send order, so that
+ *
+ *   gcl_tcp_tick -> gcl_tx_hdr -> gcl_l4_csum GCL_L4_FILL, and
+ *   gcl_tcp_rx -> gcl_tcp_rx_acks -> gcl_tx_hdr -> gcl_l4_csum GCL_L4_FILL
+ *
+ * run on one stream.  They work on every context and touch no table.
+ *
+ * The sweep of connection c at @now, on tmr[c].  All time arithmetic is
+ * uint64_t mod 2^64 and every comparison unsigned, as `now - ts >= T` reads in
+ * the reference (a ts ahead of now gives a huge difference: the timeout
+ * fires).  T in microseconds: ACK 10000, CONNECT 5000000, TIME_WAIT 1000000,
+ * ZERO_WND 300000, RETRANSMIT 300000, OOQ_ACK 300000.
+ *   1. GCL_TMR_LIVE clear, or next_timeout > now: nothing.  action = 0 and
+ *      out_tmr[c] repeats the input words (tcp.c:166).
+ *   2. action FIRED.  state == CLOSED: done, the timer is not recomputed
+ *      (:85-88).
+ *   3. state < ESTABLISHED and now - attach_ts >= CONNECT: action FAIL, the out
+ *      state is CLOSED, done (:90-95).
+ *   4. state == TIME_WAIT and now - time_wait_ts >= TIME_WAIT: action CLOSE,
+ *      the out state is CLOSED, done (:97-104).
+ *   5. ACK_DELAYED and now - ack_ts >= ACK: ACK_DELAYED is cleared, action ACK.
+ *   6. ZERO_WND and now - zero_wnd_ts >= ZERO_WND: zero_wnd_ts = now, action
+ *      PROBE.
+ *   7. not TX_EXCLUSIVE, TXQ and now - txq_ts >= RETRANSMIT: action RETRANSMIT.
+ *   8. OOO: action ACK.
+ *   9. tcp_timer_update on the words as they now stand: nt = UINT64_MAX;
+ *      TIME_WAIT: nt = time_wait_ts + TIME_WAIT; state < ESTABLISHED: nt =
+ *      attach_ts + CONNECT (it overrides the line before, as in the
+ *      reference); ACK_DELAYED: nt = min(nt, ack_ts + ACK); ZERO_WND: nt =
+ *      min(nt, zero_wnd_ts + ZERO_WND); not TX_EXCLUSIVE and TXQ: nt = min(nt,
+ *      txq_ts + RETRANSMIT); OOO: nt = min(nt, now + OOQ_ACK).
+ * In the last term the reference reads microtime() a second time; a sweep has
+ * one clock reading, @now.  That is the one departure.
+ *
+ * A control segment of connection c is a gcl_txh_desc with proto 6, tcp_flags
+ * 0x10 (ACK), tcp_off 5, ecn 0 (net_tx_ip is given a NULL aux), paylen 0, pad
+ * 0, the tuple of addr[c], the given ack, win = (uint16_t)(rcv_wnd >>
+ * (rcv_wscale & 31)) (the truncation is hton16 of a uint32_t's, as
+ * __tcp_add_tcphdr, tcp_out.c:74), and seq = conn[c].snd_nxt for an ACK,
+ * conn[c].snd_una - 1 for a window probe.
+ *
+ * Segments of a sweep come in connection order, and inside a connection the
+ * ACK before the probe (the order of tcp.c:134-137); both take ack =
+ * conn[c].rcv_nxt and rcv_wnd = conn[c].rcv_wnd.  Segment k is written exactly
+ * when k < seg_cap; a connection with a segment that was not written gets
+ * action NOSPACE.  Its timer words change all the same, as a tcp_tx_ack that
+ * returns -ENOMEM loses the ACK after ack_delayed was cleared.
+ *
+ * Segments of a gcl_tcp_rx call: list entry j emits one ACK exactly when
+ * verdict[j] == GCL_TCPRX_FAST, sflags[j] has GCL_TCPRX_SF_ACK_NOW,
+ * i = order ? order[j] : j is below n and c = sock[i] is below nconn.  They
+ * come in list order, with ack = rcv_nxt_after[j], rcv_wnd = conn[c].rcv_wnd -
+ * (rcv_nxt_after[j] - conn[c].rcv_nxt) mod 2^32 (the window as it stood after
+ * that segment) and seq = conn[c].snd_nxt.  order, n, sock, conn and nconn are
+ * those given to gcl_tcp_rx: conn is the same snapshot.
+ *
+ * Per segment k < min(wanted, seg_cap): desc[k]; frame_off[k] = frame_base +
+ * k * frame_stride (mod 2^64); seg_conn[k] = c; seg_kind[k] = GCL_CTL_ACK or
+ * GCL_CTL_PROBE; seg_src[k] = c for a sweep and the list position j for
+ * gcl_tcp_rx_acks.  Entries at and past that are not written.  totals[0] = the
+ * segments wanted, totals[1] = min(wanted, seg_cap), the m of gcl_tx_hdr.
+ * frame_stride is the caller's slot size: at least 54, and at least
+ * net.min_pkt_size when gcl_tx_hdr is to pad.
+ *
+ * @counts is a device u64[GCL_TICKC_NR], ACCUMULATED, may be NULL.  A sweep:
+ * FIRED, ACK, PROBE, RETRANSMIT, FAIL, CLOSE and NOSPACE connections, and SEGS,
+ * the segments written.  gcl_tcp_rx_acks: GCL_RXACKC_WANTED, _WRITTEN and
+ * _SKIPPED (FAST | ACK_NOW entries whose i or c is out of range).
+ *
+ * Every pointer is a device pointer; each array is aligned to its element,
+ * tmr, conn, addr, out_tmr and desc to 16 B.  Asynchronous on @hip_stream:
+ * three launches (decide, the scan of the block sums, emit) ordered by the
+ * stream alone; no block waits for another, and no atomic hands out a
+ * position: atomics only add to counts.  No allocation, no host
+ * synchronisation.  @workspace (device, 16-B aligned) need not be zeroed and
+ * may be reused by the next call on the same stream.  nconn == 0 or m == 0
+ * still writes totals.
+ *
+ * Guarantee: no content of tmr, conn, addr, order, sock, verdict, sflags or
+ * rcv_nxt_after causes a read outside the given arrays, or a write outside the
+ * first seg_cap elements of the per-segment outputs, out_tmr[0, nconn),
+ * totals, counts and the workspace.
+ *
+ * What stays with the runtime: tcp_retransmit itself (RETRANSMIT says when),
+ * tcp_conn_fail's frees and wake-ups (FAIL), tcp_conn_put (CLOSE), writing
+ * out_tmr's words back under the connection lock, and the second clock
+ * reading.
+ *
+ * gcl_tcp_tick_workspace / gcl_tcp_rx_acks_workspace - bytes of device scratch
+ *   a call takes: 4 per block (in->blocks, or the cap GCL_TICK_MAX_BLOCKS when
+ *   blocks is 0), rounded up to 16.  -EINVAL for a NULL @bytes, nconn > 2^20 or
+ *   m > 2^31, or blocks > GCL_TICK_MAX_BLOCKS.
+ * gcl_tcp_tick - -EINVAL for a NULL ctx, in or out; a wrong in->size; nconn >
+ *   2^20; seg_cap > 2^31; blocks > GCL_TICK_MAX_BLOCKS; frame_stride < 54; a
+ *   NULL totals; with nconn > 0 a NULL tmr, conn, addr or out_tmr; with
+ *   nconn > 0 and seg_cap > 0 a NULL desc, frame_off, seg_conn, seg_kind or
+ *   seg_src; any given array that is not aligned to its element; a NULL
+ *   workspace, one that is not 16-B aligned or one smaller than
+ *   gcl_tcp_tick_workspace says.  -EIO when a launch fails.
+ * gcl_tcp_rx_acks - -EINVAL for the same of its own structs, with m > 2^31 and
+ *   nconn > 2^20 as the caps; with m > 0 a NULL sock, verdict, sflags or
+ *   rcv_nxt_after; with m > 0 and nconn > 0 a NULL conn or addr; with m > 0 and
+ *   seg_cap > 0 a NULL per-segment output.  -EIO when a launch fails.
+ */
+/* enum tcp state (runtime/net/tcp.h) as gcl_tcp_tmr.state holds it */
+#define GCL_TCP_STATE_ESTABLISHED 2
+#define GCL_TCP_STATE_TIME_WAIT   8
+#define GCL_TCP_STATE_CLOSED      9
+/* gcl_tcp_tmr.flags */
+#define GCL_TMR_LIVE         0x01  /* the slot holds a connection that is on tcp_conns */
+#define GCL_TMR_ACK_DELAYED  0x02  /* c->ack_delayed */
+#define GCL_TMR_ZERO_WND     0x04  /* c->zero_wnd */
+#define GCL_TMR_TX_EXCLUSIVE 0x08  /* c->tx_exclusive */
+#define GCL_TMR_TXQ          0x10  /* !list_empty(&c->txq); txq_ts = its head's timestamp */
+#define GCL_TMR_OOO          0x20  /* !list_empty(&c->rxq_ooo) */
+/* gcl_tcp_tmr_out.action */
+#define GCL_TMRA_FIRED       0x01  /* next_timeout <= now: tcp_handle_timeouts ran */
+#define GCL_TMRA_ACK         0x02  /* tcp_tx_ack */
+#define GCL_TMRA_PROBE       0x04  /* tcp_tx_probe_window */
+#define GCL_TMRA_RETRANSMIT  0x08  /* thread_spawn(tcp_retransmit): no segment comes from this call */
+#define GCL_TMRA_FAIL        0x10  /* tcp_conn_fail(c, ETIMEDOUT) */
+#define GCL_TMRA_CLOSE       0x20  /* TIME_WAIT ran out: tcp_conn_put */
+#define GCL_TMRA_NOSPACE     0x40  /* a segment of the connection lay at or past seg_cap */
+/* seg_kind[k] */
+#define GCL_CTL_ACK   0
+#define GCL_CTL_PROBE 1
+#define GCL_TICK_MAX_BLOCKS 1024   /* the cap on in->blocks */
+#define GCL_TICK_MAX_CONN (1u << 20)
+#define GCL_CTL_MIN_STRIDE 54      /* Ethernet + IPv4 + TCP without options */
+enum { GCL_TICKC_FIRED = 0, GCL_TICKC_ACK, GCL_TICKC_PROBE, GCL_TICKC_RETRANSMIT, GCL_TICKC_FAIL,
+       GCL_TICKC_CLOSE, GCL_TICKC_NOSPACE, GCL_TICKC_SEGS, GCL_TICKC_NR = 8 };
+enum { GCL_RXACKC_WANTED = 0, GCL_RXACKC_WRITTEN, GCL_RXACKC_SKIPPED };
+struct gcl_tcp_tmr {       /* 64 B, 16-B aligned, host order: the timer words of a connection */
+	uint64_t next_timeout, attach_ts, time_wait_ts, ack_ts, zero_wnd_ts, txq_ts;  /* us, as microtime() */
+	uint8_t  state;        /* enum tcp state: SYN_SENT 0, SYN_RECEIVED 1, ESTABLISHED 2, ... */
+	uint8_t  flags;        /* GCL_TMR_* */
+	uint8_t  pad[14];
+};
+struct gcl_tcp_tmr_out {   /* 32 B, 16-B aligned */
+	uint64_t next_timeout, zero_wnd_ts;
+	uint8_t  state, flags;
+	uint8_t  action;       /* GCL_TMRA_* */
+	uint8_t  pad[13];      /* written as 0 */
+};
+struct gcl_tcp_addr {      /* 16 B: the tuple of a connection's segments, host order */
+	uint32_t lip, rip;     /* as in gcl_txh_desc */
+	uint16_t lport, rport;
+	uint8_t  rcv_wscale;   /* the low five bits are used */
+	uint8_t  pad[3];
+};
+struct gcl_ctlseg_out {                /* device, seg_cap elements each, aligned to their element */
+	struct gcl_txh_desc *desc;         /* 16-B aligned */
+	uint64_t *frame_off;
+	uint32_t *seg_conn;
+	uint8_t  *seg_kind;
+	uint32_t *seg_src;
+	uint64_t *totals;                  /* u64[2], required: wanted, written */
+};
+struct gcl_tick_in {
+	uint32_t size, blocks;             /* sizeof(struct gcl_tick_in); blocks: 0 = the library's choice, else
+	                                      the number of contiguous ranges the connections are cut into (tests) */
+	uint64_t now;                      /* us: the sweep's one clock reading */
+	const struct gcl_tcp_tmr *tmr;     /* [nconn] */
+	const struct gcl_tcp_conn *conn;   /* [nconn] */
+	const struct gcl_tcp_addr *addr;   /* [nconn] */
+	uint32_t nconn;                    /* <= 2^20 */
+	uint32_t frame_stride;             /* bytes, >= GCL_CTL_MIN_STRIDE */
+	uint64_t seg_cap;                  /* <= 2^31: the length of every per-segment output array */
+	uint64_t frame_base;
+};
+struct gcl_tick_out {
+	struct gcl_tcp_tmr_out *out_tmr;   /* [nconn] */
+	struct gcl_ctlseg_out seg;
+};
+struct gcl_rxack_in {
+	uint32_t size, blocks;             /* sizeof(struct gcl_rxack_in); blocks as in gcl_tick_in */
+	const uint32_t *order;             /* optional u32[m], as given to gcl_tcp_rx */
+	uint64_t m;                        /* list entries, <= 2^31 */
+	uint64_t n;                        /* the batch's packets: the length of sock */
+	const uint32_t *sock;              /* u32[n] */
+	const uint8_t  *verdict, *sflags;  /* u8[m], as gcl_tcp_rx wrote them */
+	const uint32_t *rcv_nxt_after;     /* u32[m], as gcl_tcp_rx wrote it */
+	const struct gcl_tcp_conn *conn;   /* [nconn]: the snapshot gcl_tcp_rx was given */
+	const struct gcl_tcp_addr *addr;   /* [nconn] */
+	uint32_t nconn;                    /* <= 2^20 */
+	uint32_t frame_stride;             /* bytes, >= GCL_CTL_MIN_STRIDE */
+	uint64_t seg_cap;                  /* <= 2^31 */
+	uint64_t frame_base;
+};
+int gcl_tcp_tick_workspace(uint32_t nconn, uint32_t blocks, size_t *bytes);
+int gcl_tcp_tick(struct gcl_ctx *ctx, const struct gcl_tick_in *in, const struct gcl_tick_out *out,
+                 uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
+int gcl_tcp_rx_acks_workspace(uint64_t m, uint32_t blocks, size_t *bytes);
+int gcl_tcp_rx_acks(struct gcl_ctx *ctx, const struct gcl_rxack_in *in, const struct gcl_ctlseg_out *out,
+                    uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
