@@ -12,6 +12,7 @@
 #include "gcl_seg.h"
 #include "gcl_tcprx.h"
 #include "gcl_tcptmr.h"
+#include "gcl_txq.h"
 #include "gcl_txh.h"
 
 #define ROT(x, k) (((x) << (k)) | ((x) >> (32 - (k))))
@@ -819,6 +820,65 @@ int gcl_tcp_rx_acks_host(const struct gcl_rxack_in *in, const struct gcl_ctlseg_
 		counts[GCL_RXACKC_WRITTEN] += out->totals[1];
 		counts[GCL_RXACKC_SKIPPED] += skipped;
 	}
+	return 0;
+}
+
+/* The rule of gcl_tcp_txq (gclassify.h) on the CPU: gcl_txq_conn of gcl_txq.h
+ * for every connection in turn, first for its count alone, as the GPU's decide
+ * launch runs it, then with the room its position leaves it. */
+int gcl_tcp_txq_host(const struct gcl_txq_in *in, const struct gcl_txq_out *out, uint64_t *counts)
+{
+	uint64_t c[GCL_TXQC_NR] = {0}, at = 0;
+
+	if (!in || !out || in->size != sizeof(*in) || in->nconn > GCL_TXQ_MAX_CONN ||
+	    in->blocks > GCL_TXQ_MAX_BLOCKS || in->nent > (1ull << 31) || in->seg_cap > (1ull << 31) ||
+	    in->frame_stride < GCL_CTL_MIN_STRIDE || !out->totals)
+		return -EINVAL;
+	if (in->nconn && (!in->qoff || !in->conn || !in->addr || !out->out_conn))
+		return -EINVAL;
+	if (in->nent && (!in->ent || !in->cold || !out->state))
+		return -EINVAL;
+	if (in->nconn && in->seg_cap && (!out->desc || !out->frame_off || !out->src_off || !out->len ||
+	                                 !out->dst_off || !out->seg_conn || !out->seg_ent))
+		return -EINVAL;
+	if (((uintptr_t)in->qoff & 3) || ((uintptr_t)in->ent & 15) || ((uintptr_t)in->cold & 15) ||
+	    ((uintptr_t)in->conn & 15) || ((uintptr_t)in->addr & 15) || ((uintptr_t)out->out_conn & 15) ||
+	    ((uintptr_t)out->desc & 15) || ((uintptr_t)out->frame_off & 7) || ((uintptr_t)out->src_off & 7) ||
+	    ((uintptr_t)out->len & 1) || ((uintptr_t)out->dst_off & 7) || ((uintptr_t)out->seg_conn & 3) ||
+	    ((uintptr_t)out->seg_ent & 3) || ((uintptr_t)out->totals & 7) || ((uintptr_t)counts & 7))
+		return -EINVAL;
+	const struct gcl_txq_call k = {out, in->now, in->frame_base, in->frame_stride};
+
+	for (uint32_t j = 0; j < in->nconn; j++) {
+		const struct gcl_tcp_conn *cn = &in->conn[j];
+		struct gcl_txq_cx x;
+		struct gcl_txq_res r;
+		uint32_t ad[4], e0, bad;
+		const uint32_t n = gcl_txq_range(in->qoff[j], in->qoff[j + 1], in->nent, &e0, &bad);
+		const uint64_t first = at < in->seg_cap ? at : in->seg_cap;
+
+		memcpy(ad, &in->addr[j], sizeof(ad)); /* little-endian host */
+		gcl_txq_cx_fill(&x, j, cn->snd_una, cn->rcv_nxt, cn->rcv_wnd, ad, in->want ? in->want[j] : 0);
+		gcl_txq_conn(&k, &x, in->ent, in->cold, e0, n, 0, GCL_TXQ_NOROOM, 0, &r);
+		at += r.nretx;
+		if (r.nretx)
+			gcl_txq_conn(&k, &x, in->ent, in->cold, e0, n, first, in->seg_cap - first, 1, &r);
+		gcl_txq_conn_out(&out->out_conn[j], &r, bad, first);
+		c[GCL_TXQC_ACKED] += r.nacked;
+		c[GCL_TXQC_RETX] += r.nretx;
+		c[GCL_TXQC_COPIED] += r.copied;
+		c[GCL_TXQC_TRIMMED] += r.trimmed;
+		c[GCL_TXQC_REFUSED] += r.refused;
+		c[GCL_TXQC_NOSPACE] += (r.flags & GCL_TXQO_NOSPACE) ? 1 : 0;
+		c[GCL_TXQC_DEFERRED] += (r.flags & GCL_TXQO_DEFERRED) ? 1 : 0;
+		c[GCL_TXQC_BYTES] += r.bytes;
+	}
+	out->totals[0] = at;
+	out->totals[1] = at < in->seg_cap ? at : in->seg_cap;
+	out->totals[2] = c[GCL_TXQC_BYTES];
+	if (counts)
+		for (int i = 0; i < GCL_TXQC_NR; i++)
+			counts[i] += c[i];
 	return 0;
 }
 

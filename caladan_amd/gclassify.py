@@ -140,6 +140,24 @@ TCP_TMR_OUT_DTYPE = np.dtype([("next_timeout", "<u8"), ("zero_wnd_ts", "<u8"), (
                               ("action", "u1"), ("pad", "u1", (13,))])
 TCP_ADDR_DTYPE = np.dtype([("lip", "<u4"), ("rip", "<u4"), ("lport", "<u2"), ("rport", "<u2"),
                            ("rcv_wscale", "u1"), ("pad", "u1", (3,))])
+# gcl_tcp_txq: the want bits, the entry flag, the state byte, the connection flags, the counters,
+# the caps, struct gcl_txq_ent, struct gcl_txq_cold and struct gcl_txq_conn_out
+TXQ_W_RTO, TXQ_W_FAST, TXQ_W_EXCL = 0x01, 0x02, 0x04
+TXQE_INFLIGHT = 0x01
+TXQS_KEPT, TXQS_ACKED, TXQS_RETX, TXQS_RETX_COPY, TXQS_NOSPACE, TXQS_REFUSED = range(6)
+TXQS_TRIMMED = 0x80
+TXQO_EMPTY, TXQO_DEFERRED, TXQO_NOSPACE, TXQO_BATCH, TXQO_BADRANGE = 0x01, 0x02, 0x04, 0x08, 0x10
+(TXQC_ACKED, TXQC_RETX, TXQC_COPIED, TXQC_TRIMMED, TXQC_REFUSED, TXQC_NOSPACE, TXQC_DEFERRED,
+ TXQC_BYTES) = range(8)
+TXQC_NR, TXQ_MAX_BLOCKS, TXQ_MAX_CONN = 8, 1024, 1 << 20
+# its launches (csrc/gcl_txq.hip): connections per tile, and the queue length from which the
+# whole wave walks a queue
+TXQ_TILE, TXQ_LONG = 256, 64
+TXQ_ENT_DTYPE = np.dtype([("seg_seq", "<u4"), ("seg_end", "<u4"), ("ts", "<u8")])
+TXQ_COLD_DTYPE = np.dtype([("frame_off", "<u8"), ("tcp_flags", "u1"), ("tcp_off", "u1"), ("flags", "u1"),
+                           ("pad", "u1", (5,))])
+TXQ_CONN_OUT_DTYPE = np.dtype([("head_ts", "<u8"), ("nacked", "<u4"), ("nretx", "<u4"), ("first", "<u4"),
+                               ("flags", "u1"), ("pad", "u1", (11,))])
 STAT_NAMES = ["RX_UNREGISTERED_MAC", "RX_UNICAST_FAIL", "RX_BROADCAST_FAIL",
               "RX_FLOW_TAG_MATCH", "RX_UNHANDLED", "RX_HASH_MISSING", "RX_PULLED"]
 
@@ -420,6 +438,24 @@ class GclRxackIn(ctypes.Structure):
                 ("frame_stride", ctypes.c_uint32), ("seg_cap", ctypes.c_uint64), ("frame_base", ctypes.c_uint64)]
 
 
+class GclTxqIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("now", ctypes.c_uint64),
+                ("qoff", ctypes.c_void_p), ("ent", ctypes.c_void_p), ("cold", ctypes.c_void_p),
+                ("nent", ctypes.c_uint64), ("conn", ctypes.c_void_p), ("addr", ctypes.c_void_p),
+                ("want", ctypes.c_void_p), ("nconn", ctypes.c_uint32), ("frame_stride", ctypes.c_uint32),
+                ("seg_cap", ctypes.c_uint64), ("frame_base", ctypes.c_uint64)]
+
+
+TXQ_SEG_FIELDS = ("desc", "frame_off", "src_off", "len", "dst_off", "seg_conn", "seg_ent")
+TXQ_OUT_FIELDS = ("out_conn", "state") + TXQ_SEG_FIELDS + ("totals",)
+
+
+class GclTxqOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in TXQ_OUT_FIELDS]
+
+
+assert ctypes.sizeof(GclTxqIn) == 96 and ctypes.sizeof(GclTxqOut) == 80
+assert TXQ_ENT_DTYPE.itemsize == 16 and TXQ_COLD_DTYPE.itemsize == 16 and TXQ_CONN_OUT_DTYPE.itemsize == 32
 assert ctypes.sizeof(GclTickIn) == 64 and ctypes.sizeof(GclTickOut) == 56 and ctypes.sizeof(GclRxackIn) == 104
 assert ctypes.sizeof(GclCtlsegOut) == 48 and TCP_TMR_DTYPE.itemsize == 64 and TCP_TMR_OUT_DTYPE.itemsize == 32
 assert TCP_ADDR_DTYPE.itemsize == 16
@@ -538,6 +574,10 @@ def _load():
         "gcl_tcp_rx_acks": (i32, [vp, ctypes.POINTER(GclRxackIn), ctypes.POINTER(GclCtlsegOut), vp, vp,
                                   ctypes.c_size_t, vp]),
         "gcl_tcp_rx_acks_host": (i32, [ctypes.POINTER(GclRxackIn), ctypes.POINTER(GclCtlsegOut), vp]),
+        "gcl_tcp_txq_workspace": (i32, [u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_txq": (i32, [vp, ctypes.POINTER(GclTxqIn), ctypes.POINTER(GclTxqOut), vp, vp,
+                              ctypes.c_size_t, vp]),
+        "gcl_tcp_txq_host": (i32, [ctypes.POINTER(GclTxqIn), ctypes.POINTER(GclTxqOut), vp]),
         "gcl_neigh_tbl_new": (vp, []),
         "gcl_neigh_tbl_free": (None, [vp]),
         "gcl_neigh_tbl_set": (i32, [vp, vp, u32]),
@@ -1186,6 +1226,66 @@ def tcp_rx_acks_workspace(m, blocks=0):
     """gcl_tcp_rx_acks_workspace: bytes of device scratch a call over @m list entries takes."""
     need = ctypes.c_size_t()
     _check(lib.gcl_tcp_rx_acks_workspace(m, blocks, ctypes.byref(need)), "gcl_tcp_rx_acks_workspace")
+    return need.value
+
+
+TXQ_OUT_WIDTH = {"desc": 32, "frame_off": 8, "src_off": 8, "len": 2, "dst_off": 8, "seg_conn": 4, "seg_ent": 4}
+
+
+def _txq_structs(now, qoff, ent, cold, nent, conn, addr, want, nconn, seg_cap, frame_base, frame_stride, blocks,
+                 out, counts):
+    """The two structs of gcl_tcp_txq / gcl_tcp_txq_host, sizes checked; @out
+    maps TXQ_OUT_FIELDS to buffers."""
+    if qoff is not None and _nbytes(qoff) < 4 * (nconn + 1):
+        raise ValueError("qoff shorter than nconn + 1")
+    for arr, w in ((conn, 48), (addr, 16), (want, 1), (out["out_conn"], 32)):
+        if arr is not None and _nbytes(arr) < w * nconn:
+            raise ValueError("per-connection array too small")
+    for arr, w in ((ent, 16), (cold, 16), (out["state"], 1)):
+        if arr is not None and _nbytes(arr) < w * nent:
+            raise ValueError("per-entry array too small")
+    for f in TXQ_SEG_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < TXQ_OUT_WIDTH[f] * seg_cap:
+            raise ValueError(f"{f}: per-segment array shorter than seg_cap")
+    if out["totals"] is not None and _nbytes(out["totals"]) < 24:
+        raise ValueError("totals too small")
+    if counts is not None and _nbytes(counts) < 8 * TXQC_NR:
+        raise ValueError("counts buffer too small")
+    qin = GclTxqIn(size=ctypes.sizeof(GclTxqIn), blocks=blocks, now=now, qoff=_ptr(qoff), ent=_ptr(ent),
+                   cold=_ptr(cold), nent=nent, conn=_ptr(conn), addr=_ptr(addr), want=_ptr(want), nconn=nconn,
+                   frame_stride=frame_stride, seg_cap=seg_cap, frame_base=frame_base)
+    return qin, GclTxqOut(**{f: _ptr(out[f]) for f in TXQ_OUT_FIELDS})
+
+
+def tcp_txq_host(now, qoff, ent, cold, conn, addr, seg_cap, want=None, frame_stride=64, frame_base=0, nconn=None,
+                 nent=None, blocks=0, out=None, counts=None):
+    """gcl_tcp_txq_host: the rule of Classifier.tcp_txq on the CPU over numpy
+    arrays.  @qoff is a u32[nconn + 1] CSR over the TXQ_ENT_DTYPE / TXQ_COLD_DTYPE
+    arrays @ent and @cold; @conn and @addr are TCP_CONN_DTYPE and TCP_ADDR_DTYPE
+    arrays indexed by cookie, @want an optional u8[nconn] of TXQ_W_* bits.  @out
+    maps TXQ_OUT_FIELDS to arrays (TXQ_CONN_OUT_DTYPE[nconn], u8[nent]; per
+    segment TXH_DESC_DTYPE, u64, u64, u16, u64, u32, u32, each @seg_cap long;
+    totals u64[3]); the ones left out are allocated.  @counts is a
+    u64[TXQC_NR], accumulated.  Returns the dict."""
+    nconn = len(conn) if nconn is None else nconn
+    nent = len(ent) if nent is None else nent
+    out = dict(out or {})
+    for f, dt, k in (("out_conn", TXQ_CONN_OUT_DTYPE, nconn), ("state", np.uint8, nent),
+                     ("desc", TXH_DESC_DTYPE, seg_cap), ("frame_off", np.uint64, seg_cap),
+                     ("src_off", np.uint64, seg_cap), ("len", np.uint16, seg_cap), ("dst_off", np.uint64, seg_cap),
+                     ("seg_conn", np.uint32, seg_cap), ("seg_ent", np.uint32, seg_cap), ("totals", np.uint64, 3)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    qin, qout = _txq_structs(now, qoff, ent, cold, nent, conn, addr, want, nconn, seg_cap, frame_base, frame_stride,
+                             blocks, out, counts)
+    _check(lib.gcl_tcp_txq_host(ctypes.byref(qin), ctypes.byref(qout), _ptr(counts)), "gcl_tcp_txq_host")
+    return out
+
+
+def tcp_txq_workspace(nconn, blocks=0):
+    """gcl_tcp_txq_workspace: bytes of device scratch a call over @nconn connections takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_txq_workspace(nconn, blocks, ctypes.byref(need)), "gcl_tcp_txq_workspace")
     return need.value
 
 
@@ -1839,6 +1939,47 @@ class Classifier:
                                                                    out["totals"].device)
         _check(lib.gcl_tcp_rx_acks(self._ctx, ctypes.byref(rin), ctypes.byref(rout), _ptr(counts), _ptr(ws),
                                    _nbytes(ws), stream), "gcl_tcp_rx_acks")
+        return out
+
+    def tcp_txq(self, now, qoff, ent, cold, nent, conn, addr, nconn, seg_cap, want=None, frame_stride=64,
+                frame_base=0, blocks=0, out=None, counts=None, workspace=None, stream=None):
+        """gcl_tcp_txq: the retransmit queues of one runtime's @nconn
+        connections at the clock reading @now (us) on the GPU, asynchronous:
+        tcp_conn_ack's pops, tcp_tx_retransmit's walk and
+        tcp_tx_fast_retransmit_start, and the retransmitted segments.  @qoff is
+        a device int32[nconn + 1] CSR over @ent and @cold, device uint8[nent,
+        16] of TXQ_ENT_DTYPE and TXQ_COLD_DTYPE records; @conn and @addr are
+        device uint8[nconn, 48 / 16] (16-B aligned), @want an optional device
+        uint8[nconn] of TXQ_W_* bits.  @out maps TXQ_OUT_FIELDS to device
+        buffers; the ones left out are allocated on @qoff's device (out_conn
+        uint8[nconn, 32], state uint8[nent]; desc uint8[seg_cap, 32],
+        frame_off, src_off and dst_off int64, len int16, seg_conn and seg_ent
+        int32; totals int64[3]).  @counts is a device u64[TXQC_NR],
+        accumulated.  The scratch is @workspace, or a torch tensor the
+        classifier keeps for this call alone (tcp_tick's is another one; two
+        tcp_txq calls in flight on different streams need a @workspace each).
+        Returns the dict: src_off, len and dst_off are
+        copy_batch's, desc and frame_off tx_hdr's, totals[1] their m."""
+        import torch
+        dev = qoff.device if hasattr(qoff, "device") else None
+        out = dict(out or {})
+        cc = max(seg_cap, 1)
+        for f, dt, shape in (("out_conn", torch.uint8, (max(nconn, 1), 32)), ("state", torch.uint8, (max(nent, 1),)),
+                             ("desc", torch.uint8, (cc, 32)), ("frame_off", torch.int64, (cc,)),
+                             ("src_off", torch.int64, (cc,)), ("len", torch.int16, (cc,)),
+                             ("dst_off", torch.int64, (cc,)), ("seg_conn", torch.int32, (cc,)),
+                             ("seg_ent", torch.int32, (cc,)), ("totals", torch.int64, (3,))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        qin, qout = _txq_structs(now, qoff, ent, cold, nent, conn, addr, want, nconn, seg_cap, frame_base,
+                                 frame_stride, blocks, out, counts)
+        ws = workspace
+        if ws is None:      # its own scratch: a sweep in flight on another stream keeps tcp_tick's
+            need, ws = tcp_txq_workspace(nconn, blocks), getattr(self, "_txq_ws_buf", None)
+            if ws is None or ws.numel() < need or ws.device != out["totals"].device:
+                ws = self._txq_ws_buf = torch.empty(need, dtype=torch.uint8, device=out["totals"].device)
+        _check(lib.gcl_tcp_txq(self._ctx, ctypes.byref(qin), ctypes.byref(qout), _ptr(counts), _ptr(ws),
+                               _nbytes(ws), stream), "gcl_tcp_txq")
         return out
 
     def copy_batch(self, src, src_off, length, n, dst, dst_off=None, dst_stride=0, tx_olflags=None,

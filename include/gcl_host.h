@@ -264,6 +264,20 @@ int gcl_tcp_tick_host(const struct gcl_tick_in *in, const struct gcl_tick_out *o
 int gcl_tcp_rx_acks_host(const struct gcl_rxack_in *in, const struct gcl_ctlseg_out *out, uint64_t *counts);
 
 /*
+ * gcl_tcp_txq_host - the rule of gcl_tcp_txq (gclassify.h) on the CPU over
+ * host pointers, for the queues the GPU did not see: tcp_conn_ack
+ * (runtime/net/tcp.c:217-238), tcp_tx_retransmit with tcp_tx_retransmit_one
+ * (runtime/net/tcp_out.c:480-506, :388-444) and tcp_tx_fast_retransmit_start
+ * (tcp_out.c:450-466) for every connection at one clock reading.  The rule is
+ * the inline code of csrc/gcl_txq.h that the kernels run, so the same inputs
+ * give the same out_conn, state, per-segment arrays and totals byte for byte,
+ * the same counts and the same guarantee.  in->blocks is checked and otherwise
+ * ignored.  0, or -EINVAL for what the call refuses (the ctx and the workspace
+ * apart).
+ */
+int gcl_tcp_txq_host(const struct gcl_txq_in *in, const struct gcl_txq_out *out, uint64_t *counts);
+
+/*
  * gcl_host_deliver - consume @n verdicts in order.
  * @clients_by_id  dp.clients_by_id (iokernel/defs.h:386), @max_runtimes long
  * @clients        dp.clients[0..nr_clients) (broadcast order, rx.c:175)

@@ -2034,6 +2034,205 @@ int gcl_tcp_rx_acks_workspace(uint64_t m, uint32_t blocks, size_t *bytes);
 int gcl_tcp_rx_acks(struct gcl_ctx *ctx, const struct gcl_rxack_in *in, const struct gcl_ctlseg_out *out,
                     uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/*
+ * The TCP retransmit queue: where the three TCP chains meet.  gcl_tx_seg cuts
+ * segments to link into c->txq, gcl_tcp_rx moves snd_una (GCL_TCPRX_SF_ACKED)
+ * and gcl_tcp_tick says when tcp_retransmit is due (GCL_TMRA_RETRANSMIT).  In
+ * the reference the queue of sent but unacknowledged segments is then walked
+ * one connection at a time under the connection lock: tcp_conn_ack
+ * (runtime/net/tcp.c:217-238), tcp_tx_retransmit with tcp_tx_retransmit_one
+ * (runtime/net/tcp_out.c:480-506, :388-444) and tcp_tx_fast_retransmit_start
+ * (tcp_out.c:450-466).  gcl_tcp_txq does those walks for all connections of
+ * one runtime at one clock reading and writes the retransmitted segments as
+ * gcl_txh_desc records, so that
+ *
+ *   gcl_tx_seg -> (txq) -> gcl_tcp_rx / gcl_tcp_tick -> gcl_tcp_txq ->
+ *   gcl_copy_batch -> gcl_tx_hdr -> gcl_l4_csum GCL_L4_FILL
+ *
+ * run on one stream.  It works on every context and touches no table.
+ *
+ * The queues come as a CSR: connection c owns entries [qoff[c], qoff[c + 1])
+ * of ent and cold, in queue order (qoff non-decreasing, qoff[nconn] == nent).
+ * ent holds what the walks read of every entry (m->seg_seq, m->seg_end,
+ * m->timestamp), cold what only a retransmitted entry needs.  conn[c] gives
+ * snd_una, rcv_nxt and rcv_wnd, addr[c] the tuple, want[c] (optional; NULL:
+ * pops only) what the runtime would run: GCL_TXQ_W_RTO tcp_retransmit,
+ * GCL_TXQ_W_FAST tcp_tx_fast_retransmit_start, GCL_TXQ_W_EXCL c->tx_exclusive.
+ * wraps_* are those of inc/base/stddef.h: wraps_gt(a, b) is (int32_t)(b - a)
+ * < 0.
+ *
+ * One connection, in the reference's order: tcp_retransmit runs
+ * tcp_tx_retransmit over the whole queue and only then does tcp_write_finish
+ * pop (tcp.c:1425-1444, :1309-1349).
+ *   1. W_EXCL: nothing happens: no pops (tcp.c:224), no walk (tcp.c:1431
+ *      waits), no fast retransmit (tcp_out.c:456).  GCL_TXQO_DEFERRED.
+ *   2. W_RTO, the walk from entry 0: break at the first entry with now - ts <
+ *      300000 (uint64_t arithmetic: ts > now counts as due, as in C);
+ *      wraps_gte(snd_una, seg_end) means continue; otherwise the entry is
+ *      WANTED: its timestamp becomes now and it is retransmitted (5).  The
+ *      walk ends after the 16th segment (TCP_RETRANSMIT_BATCH:
+ *      GCL_TXQO_BATCH), and at the first wanted entry whose segment would lie
+ *      at or past seg_cap: that entry is GCL_TXQS_NOSPACE, its timestamp has
+ *      moved, as after the -ENOMEM of tcp_out.c:410, and nothing is sent for
+ *      it.
+ *   3. Pops: nacked = the number of leading entries with !wraps_gt(seg_end,
+ *      snd_una).
+ *   4. W_FAST: entry nacked, the head after the pops, when there is one.  If
+ *      the walk did not send it, its timestamp becomes now and it is sent BY
+ *      COPY (tcp_out.c:462 raises ref, so :407 always copies); without room it
+ *      is NOSPACE.
+ *   5. A wanted entry (tcp_tx_retransmit_one): trim = wraps_lt(seg_seq,
+ *      snd_una) ? snd_una - seg_seq : 0; seq = seg_seq + trim; paylen =
+ *      seg_end - seq - ((tcp_flags & (SYN | FIN)) ? 1 : 0).  Its descriptor:
+ *      the tuple of addr[c], proto 6, ecn 0, tcp_flags and tcp_off of the
+ *      entry, seq, ack = rcv_nxt, win as a control segment's (above: the
+ *      "fresher ack" of :435), paylen, pad 0.  With k its output position:
+ *        in place (not GCL_TXQE_INFLIGHT, not the fast retransmit):
+ *          frame_off[k] = cold.frame_off + trim: the headers go back in front
+ *          of the bytes that stay; len[k] = 0, src_off[k] = cold.frame_off +
+ *          54 + trim, dst_off[k] = frame_off[k] + 54 (nothing moves).
+ *        by copy: frame_off[k] = frame_base + k * frame_stride, src_off[k] =
+ *          cold.frame_off + 54 + trim, len[k] = 4 * (tcp_off - 5) + paylen,
+ *          dst_off[k] = frame_off[k] + 54.
+ *      REFUSED (GCL_TXQS_REFUSED: nothing is emitted, its timestamp has moved,
+ *      it does not count towards the 16 and the walk goes on, like the
+ *      mbuf_free; return 0 of :428): tcp_off outside 5..15; paylen, or a
+ *      copy's len, above 65535; trim > 0 with tcp_off > 5; a copied frame (54
+ *      + len) longer than frame_stride.  A refused entry asks for no room: it
+ *      is REFUSED, not NOSPACE, wherever seg_cap lies.
+ * Two departures from the reference.  It computes l4len before the partial-ACK
+ * pull and never again (:395 against :431) and so seeds the checksum with the
+ * untrimmed length: the descriptor carries the trimmed one.  And with options
+ * and a partial ACK it pulls option bytes: such an entry is refused here (only
+ * a SYN carries options and a SYN has sequence length 1, so consistent input
+ * never gets there).  The test of :427 can hold for a wanted entry only when
+ * seg_end lies exactly 2^31 past snd_una, which no consistent queue has: such
+ * an entry is sent by the rules above and reported ACKED.
+ *
+ * Per connection out_conn[c], every byte written: nacked; nretx, the segments
+ * written for it; first = min(the segments wanted by the connections before
+ * it, seg_cap), the position of its first segment; head_ts, the timestamp of
+ * entry nacked after the call (0 without one): the txq_ts of the next
+ * gcl_tcp_tmr; flags: GCL_TXQO_EMPTY (nacked is the whole queue: clear
+ * GCL_TMR_TXQ), DEFERRED, NOSPACE, BATCH, and GCL_TXQO_BADRANGE: a range that
+ * is inverted or not inside [0, nent] is treated as an empty queue.
+ * Per entry state[e], for every e of a valid range (an entry no range covers
+ * is not written): GCL_TXQS_KEPT, ACKED (free it), RETX, RETX_COPY, NOSPACE or
+ * REFUSED, the sent ones ORed with GCL_TXQS_TRIMMED when trim > 0 (the host
+ * sets m->seg_seq = snd_una); every state from RETX on means m->timestamp =
+ * now.  An ACKED entry that was also retransmitted is ACKED.
+ * Per segment k < totals[1], in connection order and then queue order: desc,
+ * frame_off, src_off, len and dst_off as above (the types of gcl_seg_out:
+ * gcl_copy_batch passes over len 0), seg_conn[k] = c and seg_ent[k] = e.
+ * Entries at and past totals[1] are not written.  totals[0] = the segments
+ * wanted (what seg_cap should have been), totals[1] = min(wanted, seg_cap),
+ * totals[2] = the sum of len[].
+ *
+ * @counts is a device u64[GCL_TXQC_NR], ACCUMULATED, may be NULL: ACKED
+ * entries, RETX segments written, those COPIED and those TRIMMED, REFUSED
+ * entries, NOSPACE and DEFERRED connections, and BYTES (totals[2]).
+ *
+ * Every pointer is a device pointer; each array is aligned to its element,
+ * ent, cold, conn, addr, out_conn and desc to 16 B.  Asynchronous on
+ * @hip_stream: three launches (decide, the scan of the block sums, emit)
+ * ordered by the stream alone; no block waits for another and no atomic hands
+ * out a position: atomics only add to counts and to the byte sum totals[2].
+ * No allocation, no host synchronisation.  @workspace (device, 16-B aligned)
+ * need not be zeroed and may be reused by the next call on the same stream.
+ * nconn == 0 still writes totals.
+ *
+ * Guarantee: no content of qoff, ent, cold, conn, addr or want causes a read
+ * outside the given arrays, or a write outside the first seg_cap elements of
+ * the per-segment outputs, out_conn[0, nconn), state[0, nent), totals, counts
+ * and the workspace.  Garbage qoff is included: decreasing values, or values
+ * past nent.  Ranges that overlap, which only a decreasing qoff produces, are
+ * each walked; state[e] of an entry two of them share is that of either.
+ *
+ * What stays with the runtime: the frees themselves, tcp_write_finish's
+ * wake-ups, do_fast_retransmit's bookkeeping (the caller decides W_FAST),
+ * writing the timestamps and seg_seq back, and the lock.
+ *
+ * gcl_tcp_txq_workspace - bytes of device scratch a call takes: 4 per block
+ *   (in->blocks, or the cap GCL_TXQ_MAX_BLOCKS when blocks is 0), rounded up
+ *   to 16.  -EINVAL for a NULL @bytes, nconn > 2^20 or blocks >
+ *   GCL_TXQ_MAX_BLOCKS.
+ * gcl_tcp_txq - -EINVAL for a NULL ctx, in or out; a wrong in->size; nconn >
+ *   2^20; nent or seg_cap > 2^31; blocks > GCL_TXQ_MAX_BLOCKS; frame_stride <
+ *   54; a NULL totals; with nconn > 0 a NULL qoff, conn, addr or out_conn; with
+ *   nent > 0 a NULL ent, cold or state; with nconn > 0 and seg_cap > 0 a NULL
+ *   per-segment output; any given array that is not aligned to its element; a
+ *   NULL workspace, one that is not 16-B aligned or one smaller than
+ *   gcl_tcp_txq_workspace says.  -EIO when a launch fails.
+ */
+/* want[c] */
+#define GCL_TXQ_W_RTO      0x01  /* GCL_TMRA_RETRANSMIT fired: tcp_retransmit */
+#define GCL_TXQ_W_FAST     0x02  /* tcp_tx_fast_retransmit_start */
+#define GCL_TXQ_W_EXCL     0x04  /* c->tx_exclusive */
+/* gcl_txq_cold.flags */
+#define GCL_TXQE_INFLIGHT  0x01  /* atomic_read(&m->ref) != 1 */
+/* state[e] */
+#define GCL_TXQS_KEPT      0
+#define GCL_TXQS_ACKED     1
+#define GCL_TXQS_RETX      2
+#define GCL_TXQS_RETX_COPY 3
+#define GCL_TXQS_NOSPACE   4
+#define GCL_TXQS_REFUSED   5
+#define GCL_TXQS_TRIMMED   0x80
+/* gcl_txq_conn_out.flags */
+#define GCL_TXQO_EMPTY     0x01
+#define GCL_TXQO_DEFERRED  0x02
+#define GCL_TXQO_NOSPACE   0x04
+#define GCL_TXQO_BATCH     0x08
+#define GCL_TXQO_BADRANGE  0x10
+#define GCL_TXQ_MAX_BLOCKS 1024    /* the cap on in->blocks */
+#define GCL_TXQ_MAX_CONN (1u << 20)
+enum { GCL_TXQC_ACKED = 0, GCL_TXQC_RETX, GCL_TXQC_COPIED, GCL_TXQC_TRIMMED, GCL_TXQC_REFUSED,
+       GCL_TXQC_NOSPACE, GCL_TXQC_DEFERRED, GCL_TXQC_BYTES, GCL_TXQC_NR = 8 };
+struct gcl_txq_ent {       /* 16 B: m->seg_seq, m->seg_end, m->timestamp */
+	uint32_t seg_seq, seg_end;
+	uint64_t ts;
+};
+struct gcl_txq_cold {      /* 16 B */
+	uint64_t frame_off;    /* where the segment's Ethernet header lies in the tx region */
+	uint8_t  tcp_flags, tcp_off;
+	uint8_t  flags;        /* GCL_TXQE_* */
+	uint8_t  pad[5];
+};
+struct gcl_txq_conn_out {  /* 32 B, 16-B aligned */
+	uint64_t head_ts;
+	uint32_t nacked, nretx, first;
+	uint8_t  flags;        /* GCL_TXQO_* */
+	uint8_t  pad[11];      /* written as 0 */
+};
+struct gcl_txq_in {
+	uint32_t size, blocks;             /* sizeof(struct gcl_txq_in); blocks as in gcl_tick_in */
+	uint64_t now;                      /* us: the call's one clock reading */
+	const uint32_t *qoff;              /* u32[nconn + 1] */
+	const struct gcl_txq_ent *ent;     /* [nent] */
+	const struct gcl_txq_cold *cold;   /* [nent] */
+	uint64_t nent;                     /* <= 2^31 */
+	const struct gcl_tcp_conn *conn;   /* [nconn] */
+	const struct gcl_tcp_addr *addr;   /* [nconn] */
+	const uint8_t *want;               /* optional u8[nconn] */
+	uint32_t nconn;                    /* <= 2^20 */
+	uint32_t frame_stride;             /* bytes, >= GCL_CTL_MIN_STRIDE: the slots of copied segments */
+	uint64_t seg_cap;                  /* <= 2^31: the length of every per-segment output array */
+	uint64_t frame_base;
+};
+struct gcl_txq_out {                   /* device, aligned to their element */
+	struct gcl_txq_conn_out *out_conn; /* [nconn] */
+	uint8_t  *state;                   /* [nent] */
+	struct gcl_txh_desc *desc;         /* [seg_cap], 16-B aligned */
+	uint64_t *frame_off, *src_off;     /* [seg_cap] */
+	uint16_t *len;                     /* [seg_cap] */
+	uint64_t *dst_off;                 /* [seg_cap] */
+	uint32_t *seg_conn, *seg_ent;      /* [seg_cap] */
+	uint64_t *totals;                  /* u64[3], required: wanted, written, bytes to copy */
+};
+int gcl_tcp_txq_workspace(uint32_t nconn, uint32_t blocks, size_t *bytes);
+int gcl_tcp_txq(struct gcl_ctx *ctx, const struct gcl_txq_in *in, const struct gcl_txq_out *out,
+                uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
