@@ -11,6 +11,7 @@
 #include "gcl_pay.h"
 #include "gcl_seg.h"
 #include "gcl_tcprx.h"
+#include "gcl_tcprxf.h"
 #include "gcl_tcptmr.h"
 #include "gcl_txq.h"
 #include "gcl_txh.h"
@@ -703,6 +704,131 @@ int gcl_tcp_rx_host(const struct gcl_batch *b, const struct gcl_tcprx_in *in,
 		}
 	if (counts)
 		for (int k = 0; k < GCL_TCPRXC_NR; k++)
+			counts[k] += c[k];
+	return 0;
+}
+
+/* The rule of gcl_tcp_rx_full (gclassify.h) on the CPU: gcl_tcp_rx_host's walk
+ * with gcl_tcprxf_one of gcl_tcprxf.h for every segment, every connection's
+ * live words kept in out_conn and out_ext. */
+int gcl_tcp_rx_full_host(const struct gcl_batch *b, const struct gcl_tcprxf_in *fin,
+                         const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext, uint64_t *counts)
+{
+	uint64_t c[GCL_TCPRXFC_NR] = {0}, at = 0;
+
+	if (!b || !fin || !out || fin->size != sizeof(*fin))
+		return -EINVAL;
+	const struct gcl_tcprx_in rin = {sizeof(rin), fin->align, fin->order, fin->m, fin->sock, fin->l4_status,
+	                                 fin->conn, fin->nconn, fin->blocks};
+	const struct gcl_tcprx_in *in = &rin;
+
+	if (!gcl_pay_align_ok(in->align) ||
+	    (!in->order && in->m != b->n) || in->m > (1ull << 31) || in->nconn > GCL_TCPRX_MAX_CONN ||
+	    in->blocks > GCL_TCPRX_MAX_BLOCKS || !in->sock || !out->conn_off)
+		return -EINVAL;
+	if (in->nconn && (!in->conn || !out->out_conn || !out_ext))
+		return -EINVAL;
+	if (in->m && (!out->verdict || !out->sflags || !out->rcv_nxt_after || !out->copy_len || !out->dst_off))
+		return -EINVAL;
+	if (((uintptr_t)in->order & 3) || ((uintptr_t)in->sock & 3) || ((uintptr_t)in->conn & 15) ||
+	    ((uintptr_t)out->rcv_nxt_after & 3) || ((uintptr_t)out->copy_len & 1) || ((uintptr_t)out->dst_off & 7) ||
+	    ((uintptr_t)out->out_conn & 15) || ((uintptr_t)out->conn_off & 7) || ((uintptr_t)counts & 7) ||
+	    ((uintptr_t)out_ext & 15))
+		return -EINVAL;
+	if (in->m && (!b->frames || b->frames_len == UINT64_MAX || b->n > (1ull << 40) ||
+	              (!b->offs && (b->stride < 16 || (b->stride & 15) || b->stride > (1u << 20))) ||
+	              !b->pkt_len || ((uintptr_t)b->pkt_len & 1)))
+		return -EINVAL;
+	const uint32_t amask = in->align ? in->align - 1 : 0;
+
+	for (uint32_t k = 0; k < in->nconn; k++) {
+		const struct gcl_tcp_conn *cn = &in->conn[k];
+		struct gcl_tcp_conn_out *o = &out->out_conn[k];
+
+		memset(o, 0, sizeof(*o));
+		o->snd_una = cn->snd_una;
+		o->snd_wnd = cn->snd_wnd;
+		o->snd_wl1 = cn->snd_wl1;
+		o->snd_wl2 = cn->snd_wl2;
+		o->rcv_nxt = cn->rcv_nxt;
+		o->rcv_wnd = cn->rcv_wnd;
+		o->first_slow = GCL_TCPRX_NONE;
+		o->acks_delayed_cnt = cn->acks_delayed_cnt;
+		o->flags = cn->flags & (GCL_TCPC_RXQ | GCL_TCPC_ACK_DELAYED);
+		memset(&out_ext[k], 0, sizeof(out_ext[k]));
+		out_ext[k].rep_acks = fin->rep_acks ? fin->rep_acks[k] : 0;
+	}
+	for (uint64_t j = 0; j < in->m; j++) {
+		struct gcl_tcprx_seg s = {0, 0, 0, 0, 0};
+		const uint32_t k = tcprx_entry(b, in, j, &s);
+		uint32_t verdict, sf = 0, after = 0, len = 0;
+
+		if (k == GCL_TCPRX_NONE) {
+			verdict = GCL_TCPRX_NA;
+		} else if (k >= in->nconn) {
+			verdict = GCL_TCPRX_NOCONN;
+		} else if (s.len > in->conn[k].rcv_mss) {
+			verdict = GCL_TCPRX_DROP;
+		} else {
+			struct gcl_tcp_conn_out *o = &out->out_conn[k];
+			struct gcl_tcp_conn_ext *e = &out_ext[k];
+			struct gcl_tcprxf_live x = {{o->snd_una, o->snd_wnd, o->snd_wl1, o->snd_wl2, o->rcv_nxt,
+			                             o->rcv_wnd, o->acks_delayed_cnt, o->flags},
+			                            e->rep_acks, e->fast_rtx_ack, e->xflags};
+			const int stopped = (x.l.flags & GCL_TCPO_STOPPED) != 0;
+
+			verdict = gcl_tcprxf_one(&in->conn[k], &x, &s, &sf, &len);
+			if (verdict == GCL_TCPRX_FAST) {
+				o->snd_una = x.l.snd_una;
+				o->snd_wnd = x.l.snd_wnd;
+				o->snd_wl1 = x.l.snd_wl1;
+				o->snd_wl2 = x.l.snd_wl2;
+				o->rcv_nxt = x.l.rcv_nxt;
+				o->rcv_wnd = x.l.rcv_wnd;
+				o->acks_delayed_cnt = (uint8_t)x.l.cnt;
+				o->nfast++;
+				o->nacks += (sf & GCL_TCPRX_SF_ACK_NOW) != 0;
+				e->nrule2 += (sf & GCL_TCPRX_SF_RULE2) != 0;
+				e->ndropped += (sf & GCL_TCPRX_SF_DROPPED) != 0;
+				e->fast_rtx_ack = x.fast_rtx_ack;
+				e->rep_acks = (uint8_t)x.rep_acks;
+				e->xflags = (uint8_t)x.xflags;
+				after = x.l.rcv_nxt;
+				c[GCL_TCPRXC_BYTES] += len;
+				c[GCL_TCPRXC_ACKS] += (sf & GCL_TCPRX_SF_ACK_NOW) != 0;
+				c[GCL_TCPRXC_WAKES] += (sf & GCL_TCPRX_SF_WAKE) != 0;
+				c[GCL_TCPRXFC_RULE2] += (sf & GCL_TCPRX_SF_RULE2) != 0;
+				c[GCL_TCPRXFC_TXWAKES] += (sf & GCL_TCPRX_SF_TXWAKE) != 0;
+				c[GCL_TCPRXFC_FASTRTX] += (sf & GCL_TCPRX_SF_FASTRTX) != 0;
+				c[GCL_TCPRXFC_DUPACKS] += (sf & GCL_TCPRXF_EV_DUPACK) != 0;
+				c[GCL_TCPRXFC_DROPPED] += (sf & GCL_TCPRX_SF_DROPPED) != 0;
+			} else {
+				o->nslow++;
+				if (!stopped)
+					o->first_slow = (uint32_t)j;
+			}
+			o->flags = (uint8_t)x.l.flags;
+		}
+		out->verdict[j] = (uint8_t)verdict;
+		out->sflags[j] = (uint8_t)sf;
+		out->rcv_nxt_after[j] = after;
+		out->copy_len[j] = (uint16_t)len;
+		/* for now the offset inside the connection's region */
+		out->dst_off[j] = len ? (uint32_t)(s.seq - in->conn[k].rcv_nxt) : 0;
+		c[verdict]++;
+	}
+	for (uint32_t k = 0; k < in->nconn; k++) {
+		out->conn_off[k] = at;
+		at += gcl_tcprx_pad((uint32_t)(out->out_conn[k].rcv_nxt - in->conn[k].rcv_nxt), amask);
+	}
+	out->conn_off[in->nconn] = at;
+	for (uint64_t j = 0; j < in->m; j++)
+		if (out->copy_len[j]) {
+			const uint64_t i = in->order ? in->order[j] : j;
+			out->dst_off[j] += out->conn_off[in->sock[i]];
+		}
+	if (counts)
+		for (int k = 0; k < GCL_TCPRXFC_NR; k++)
 			counts[k] += c[k];
 	return 0;
 }

@@ -44,6 +44,11 @@
  *            (only with counts) sums the connections' counters: an add per
  *            counter per block.
  *
+ * gcl_tcp_rx_full (the rule of gcl_tcprxf.h) shares every launch but three:
+ * its walk is serial over the chunk (rxf_walk_kernel), its fix-up keys on
+ * copy_len, and its counter kernel sums ten counters; both entry points go
+ * through rx_run, and gcl_tcp_rx launches what it always launched.
+ *
  * Bounds.  A list index is used only below m, a packet index only below n, a
  * cookie only below nconn (parse leaves no other in the workspace, and every
  * later use clamps again); sorted positions are stored only below m; the
@@ -63,6 +68,7 @@
 #include "gcl_ctx.h"
 #include "gcl_pay.h"
 #include "gcl_tcprx.h"
+#include "gcl_tcprxf.h"
 
 namespace gclk {
 
@@ -589,6 +595,170 @@ __global__ void __launch_bounds__(kRxThreads) rx_counts_kernel(RxParams k)
 	}
 }
 
+/* ---- gcl_tcp_rx_full: its walk, its layout fix and its counters ---- */
+
+struct RxfParams {
+	RxParams k;
+	const uint8_t *rep_acks; /* [nconn] or NULL */
+	uint4 *out_ext;          /* struct gcl_tcp_conn_ext as one 16-B word */
+	uint4 *xcnt;             /* the workspace, [nconn]: TXWAKE, FASTRTX and rep_acks++ segments */
+};
+
+__device__ __forceinline__ uint32_t rx_pop(bool b)
+{
+	return (uint32_t)__popcll(__ballot(b));
+}
+
+/*
+ * One wave per connection, as rx_walk_kernel.  An unaccepted segment does not
+ * move rcv_nxt, so the stop is no prefix sum: the wave walks the chunk's
+ * records serially, wave-uniform, each read out of its lane, through
+ * gcl_tcprxf_one; a lane keeps what its own record got, and the counters are
+ * ballots over the chunk afterwards.
+ */
+__global__ void __launch_bounds__(kRxThreads) rxf_walk_kernel(RxfParams p, const uint32_t *sorted)
+{
+	const RxParams &k = p.k;
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRxWaves + (threadIdx.x >> 6)));
+
+	if (c >= k.nconn)
+		return;
+	struct gcl_tcp_conn cn;
+	{
+		const uint4 a = k.conn[3 * (size_t)c], b = k.conn[3 * (size_t)c + 1], d = k.conn[3 * (size_t)c + 2];
+		cn.snd_una = a.x; cn.snd_nxt = a.y; cn.snd_wnd = a.z; cn.snd_wl1 = a.w;
+		cn.snd_wl2 = b.x; cn.rcv_nxt = b.y; cn.rcv_wnd = b.z;
+		cn.rcv_mss = (uint16_t)b.w; cn.snd_wscale = (uint8_t)(b.w >> 16); cn.flags = (uint8_t)(b.w >> 24);
+		cn.acks_delayed_cnt = (uint8_t)d.x;
+	}
+	struct gcl_tcprxf_live x;
+	x.l = gcl_tcprx_live_of(&cn);
+	x.rep_acks = p.rep_acks ? p.rep_acks[c] : 0;
+	x.fast_rtx_ack = 0;
+	x.xflags = 0;
+	const uint2 rn = k.run[c];
+	const uint64_t re = rn.y < k.m ? rn.y : k.m;
+	const uint64_t rs = rn.x < re ? rn.x : re;
+	uint32_t nfast = 0, nslow = 0, nacks = 0, wakes = 0, first_slow = GCL_TCPRX_NONE;
+	uint32_t nrule2 = 0, ndropped = 0, ntxw = 0, nfrtx = 0, ndup = 0;
+
+	for (uint64_t base = rs; base < re; base += 64) { /* uniform */
+		const uint32_t nv = re - base < 64 ? (uint32_t)(re - base) : 64;
+		const bool valid = lane < nv;
+		uint32_t j = valid ? sorted[base + lane] : 0;
+		if (j >= k.m)
+			j = (uint32_t)(k.m - 1);
+		const uint4 rec = valid ? k.rec[j] : make_uint4(0, 0, 0, 0);
+		const bool stopped = (x.l.flags & GCL_TCPO_STOPPED) != 0;
+		uint32_t H = 0, sf_mine = 0, after_mine = 0, copy_mine = 0;
+
+		if (!stopped) {
+			H = nv;
+			for (uint32_t at = 0; at < nv; at++) { /* uniform */
+				const uint32_t z = rx_lane(rec.z, at);
+				const struct gcl_tcprx_seg s = {rx_lane(rec.x, at), rx_lane(rec.y, at), z & 0xFFFFu,
+				                                rx_lane(rec.w, at), z >> 16};
+				uint32_t sf, cp;
+				if (gcl_tcprxf_one(&cn, &x, &s, &sf, &cp) != GCL_TCPRX_FAST) {
+					H = at;
+					break;
+				}
+				if (lane == at) {
+					sf_mine = sf;
+					after_mine = x.l.rcv_nxt;
+					copy_mine = cp;
+				}
+			}
+		}
+		nfast += H;
+		nslow += nv - H;
+		if (H < nv) {
+			if (!stopped)
+				first_slow = rx_lane(j, H);
+			x.l.flags |= GCL_TCPO_STOPPED;
+		}
+		if (H) { /* lanes at and past H hold 0 */
+			nacks += rx_pop(sf_mine & GCL_TCPRX_SF_ACK_NOW);
+			wakes += rx_pop(sf_mine & GCL_TCPRX_SF_WAKE);
+			nrule2 += rx_pop(sf_mine & GCL_TCPRX_SF_RULE2);
+			ndropped += rx_pop(sf_mine & GCL_TCPRX_SF_DROPPED);
+			ntxw += rx_pop(sf_mine & GCL_TCPRX_SF_TXWAKE);
+			nfrtx += rx_pop(sf_mine & GCL_TCPRX_SF_FASTRTX);
+			ndup += rx_pop(sf_mine & GCL_TCPRXF_EV_DUPACK);
+		}
+		if (valid) {
+			k.verdict[j] = (uint8_t)(lane < H ? GCL_TCPRX_FAST : GCL_TCPRX_SLOW);
+			k.sflags[j] = (uint8_t)sf_mine;
+			k.after[j] = after_mine;
+			k.copy_len[j] = (uint16_t)copy_mine;
+			k.dst_off[j] = copy_mine ? (uint32_t)(rec.x - cn.rcv_nxt) : 0; /* layout adds conn_off[c] */
+		}
+	}
+	if (lane == 0) {
+		k.out_conn[3 * (size_t)c] = make_uint4(x.l.snd_una, x.l.snd_wnd, x.l.snd_wl1, x.l.snd_wl2);
+		k.out_conn[3 * (size_t)c + 1] = make_uint4(x.l.rcv_nxt, x.l.rcv_wnd, nfast, nslow);
+		k.out_conn[3 * (size_t)c + 2] = make_uint4(nacks, first_slow, (x.l.cnt & 0xFFu) | (x.l.flags & 0xFFu) << 8, 0);
+		p.out_ext[c] = make_uint4(nrule2, ndropped, x.fast_rtx_ack, (x.rep_acks & 0xFFu) | (x.xflags & 0xFFu) << 8);
+		p.xcnt[c] = make_uint4(ntxw, nfrtx, ndup, 0);
+		k.wakes[c] = wakes;
+	}
+}
+
+__global__ void __launch_bounds__(kRxThreads) rxf_fix_kernel(RxParams k)
+{
+	for (uint64_t j = (uint64_t)blockIdx.x * kRxThreads + threadIdx.x; j < k.m;
+	     j += (uint64_t)gridDim.x * kRxThreads) {
+		const uint32_t c = k.cookie[j];
+		if (c < k.nconn && k.copy_len[j])
+			k.dst_off[j] += k.conn_off[c];
+	}
+}
+
+/* the ten counters of the call that the walk decides, summed over the connections */
+__global__ void __launch_bounds__(kRxThreads) rxf_counts_kernel(RxfParams p)
+{
+	constexpr int N = 10;
+	const RxParams &k = p.k;
+	__shared__ unsigned long long blk[N];
+	unsigned long long v[N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+	if (threadIdx.x < N)
+		blk[threadIdx.x] = 0;
+	__syncthreads();
+	for (uint32_t c = blockIdx.x * kRxThreads + threadIdx.x; c < k.nconn; c += gridDim.x * kRxThreads) {
+		const uint4 o1 = k.out_conn[3 * (size_t)c + 1], o2 = k.out_conn[3 * (size_t)c + 2];
+		const uint4 e = p.out_ext[c], xc = p.xcnt[c];
+		v[0] += o1.z;
+		v[1] += o1.w;
+		v[2] += (uint32_t)(o1.x - k.conn[3 * (size_t)c + 1].y);
+		v[3] += o2.x;
+		v[4] += k.wakes[c];
+		v[5] += e.x;
+		v[6] += xc.x;
+		v[7] += xc.y;
+		v[8] += xc.z;
+		v[9] += e.y;
+	}
+#pragma unroll
+	for (int x = 0; x < N; x++) {
+		for (int d = 32; d; d >>= 1) {
+			const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v[x], d);
+			const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v[x] >> 32), d);
+			v[x] += (unsigned long long)hi << 32 | lo;
+		}
+		if ((threadIdx.x & 63) == 0 && v[x])
+			atomicAdd(&blk[x], v[x]);
+	}
+	__syncthreads();
+	if (threadIdx.x < N && blk[threadIdx.x]) {
+		const uint32_t slot[N] = {GCL_TCPRXC_FAST, GCL_TCPRXC_SLOW, GCL_TCPRXC_BYTES, GCL_TCPRXC_ACKS,
+		                          GCL_TCPRXC_WAKES, GCL_TCPRXFC_RULE2, GCL_TCPRXFC_TXWAKES, GCL_TCPRXFC_FASTRTX,
+		                          GCL_TCPRXFC_DUPACKS, GCL_TCPRXFC_DROPPED};
+		atomicAdd(k.counts + slot[threadIdx.x], blk[threadIdx.x]);
+	}
+}
+
 /* ---- the workspace ---- */
 
 struct RxGeom {
@@ -664,9 +834,15 @@ extern "C" int gcl_tcp_rx_workspace(uint64_t m, uint32_t nconn, uint32_t blocks,
 	return 0;
 }
 
-extern "C" int gcl_tcp_rx(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprx_in *in,
-                          const struct gcl_tcprx_out *out, uint64_t *counts, void *workspace,
-                          size_t workspace_bytes, void *hip_stream)
+/* what gcl_tcp_rx_full adds to a call; NULL: gcl_tcp_rx */
+struct RxFull {
+	const uint8_t *rep_acks;
+	struct gcl_tcp_conn_ext *out_ext;
+};
+
+static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprx_in *in,
+                  const struct gcl_tcprx_out *out, const RxFull *full, uint64_t *counts, void *workspace,
+                  size_t workspace_bytes, void *hip_stream)
 {
 	hipStream_t s = (hipStream_t)hip_stream;
 	RxGeom g;
@@ -675,7 +851,9 @@ extern "C" int gcl_tcp_rx(struct gcl_ctx *c, const struct gcl_batch *b, const st
 	    (!in->order && in->m != b->n) || rx_geometry(in->m, in->nconn, in->blocks, &g) || !in->sock ||
 	    !out->conn_off)
 		return -EINVAL;
-	if (in->nconn && (!in->conn || !out->out_conn))
+	if (in->nconn && (!in->conn || !out->out_conn || (full && !full->out_ext)))
+		return -EINVAL;
+	if (full && rx_misaligned(full->out_ext, 16))
 		return -EINVAL;
 	if (in->m && (!out->verdict || !out->sflags || !out->rcv_nxt_after || !out->copy_len || !out->dst_off))
 		return -EINVAL;
@@ -684,7 +862,9 @@ extern "C" int gcl_tcp_rx(struct gcl_ctx *c, const struct gcl_batch *b, const st
 	    rx_misaligned(out->dst_off, 8) || rx_misaligned(out->out_conn, 16) ||
 	    rx_misaligned(out->conn_off, 8) || rx_misaligned(counts, 8))
 		return -EINVAL;
-	if (!workspace || rx_misaligned(workspace, 16) || workspace_bytes < g.bytes)
+	/* gcl_tcp_rx_full keeps xcnt behind gcl_tcp_rx's workspace */
+	const size_t xbytes = full ? 16 * (size_t)in->nconn : 0;
+	if (!workspace || rx_misaligned(workspace, 16) || workspace_bytes < g.bytes + xbytes)
 		return -EINVAL;
 	if (in->m && (!b->frames || b->frames_len == UINT64_MAX || b->n > (1ull << 40) ||
 	              (!b->offs && (b->stride < 16 || (b->stride & 15) || b->stride > (1u << 20))) ||
@@ -765,8 +945,17 @@ extern "C" int gcl_tcp_rx(struct gcl_ctx *c, const struct gcl_batch *b, const st
 		}
 		hipLaunchKernelGGL(rx_runs_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k, sorted);
 	}
-	hipLaunchKernelGGL(rx_walk_kernel, dim3((in->nconn + kRxWaves - 1) / kRxWaves), dim3(kRxThreads), 0, s, k,
-	                   sorted);
+	RxfParams kf = {k, nullptr, nullptr, nullptr};
+	if (full) {
+		kf.rep_acks = full->rep_acks;
+		kf.out_ext = (uint4 *)full->out_ext;
+		kf.xcnt = (uint4 *)(ws + g.bytes);
+		hipLaunchKernelGGL(rxf_walk_kernel, dim3((in->nconn + kRxWaves - 1) / kRxWaves), dim3(kRxThreads), 0, s,
+		                   kf, sorted);
+	} else {
+		hipLaunchKernelGGL(rx_walk_kernel, dim3((in->nconn + kRxWaves - 1) / kRxWaves), dim3(kRxThreads), 0, s, k,
+		                   sorted);
+	}
 	{
 		const RxConnIo io = {k.conn, k.out_conn, k.conn_off, in->nconn, k.amask};
 		const uint32_t nchunks = (in->nconn + kRxChunk - 1) / kRxChunk;
@@ -775,11 +964,47 @@ extern "C" int gcl_tcp_rx(struct gcl_ctx *c, const struct gcl_batch *b, const st
 		hipLaunchKernelGGL(rx_scan_apply_kernel<RxConnIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn,
 		                   k.lsum);
 	}
-	if (in->m)
-		hipLaunchKernelGGL(rx_fix_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
-	if (counts)
-		hipLaunchKernelGGL(rx_counts_kernel,
-		                   dim3(std::min<uint32_t>((in->nconn + kRxThreads - 1) / kRxThreads, cus * 2)),
-		                   dim3(kRxThreads), 0, s, k);
+	const dim3 cgrid(std::min<uint32_t>((in->nconn + kRxThreads - 1) / kRxThreads, cus * 2));
+	if (full) {
+		if (in->m)
+			hipLaunchKernelGGL(rxf_fix_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
+		if (counts)
+			hipLaunchKernelGGL(rxf_counts_kernel, cgrid, dim3(kRxThreads), 0, s, kf);
+	} else {
+		if (in->m)
+			hipLaunchKernelGGL(rx_fix_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
+		if (counts)
+			hipLaunchKernelGGL(rx_counts_kernel, cgrid, dim3(kRxThreads), 0, s, k);
+	}
 	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+extern "C" int gcl_tcp_rx(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprx_in *in,
+                          const struct gcl_tcprx_out *out, uint64_t *counts, void *workspace,
+                          size_t workspace_bytes, void *hip_stream)
+{
+	return rx_run(c, b, in, out, nullptr, counts, workspace, workspace_bytes, hip_stream);
+}
+
+extern "C" int gcl_tcp_rx_full_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, size_t *bytes)
+{
+	RxGeom g;
+
+	if (!bytes || rx_geometry(m, nconn, blocks, &g))
+		return -EINVAL;
+	*bytes = g.bytes + 16 * (size_t)nconn;
+	return 0;
+}
+
+extern "C" int gcl_tcp_rx_full(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprxf_in *in,
+                               const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext,
+                               uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+	if (!in || in->size != sizeof(*in))
+		return -EINVAL;
+	const struct gcl_tcprx_in rin = {sizeof(rin), in->align, in->order, in->m, in->sock, in->l4_status,
+	                                 in->conn, in->nconn, in->blocks};
+	const RxFull full = {in->rep_acks, out_ext};
+
+	return rx_run(c, b, &rin, out, &full, counts, workspace, workspace_bytes, hip_stream);
 }

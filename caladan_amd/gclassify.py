@@ -119,6 +119,13 @@ TCP_CONN_OUT_DTYPE = np.dtype([("snd_una", "<u4"), ("snd_wnd", "<u4"), ("snd_wl1
                                ("rcv_nxt", "<u4"), ("rcv_wnd", "<u4"), ("nfast", "<u4"), ("nslow", "<u4"),
                                ("nacks", "<u4"), ("first_slow", "<u4"), ("acks_delayed_cnt", "u1"),
                                ("flags", "u1"), ("pad", "u1", (6,))])
+# gcl_tcp_rx_full: the sflags it adds, gcl_tcp_conn_ext.xflags, the counters behind gcl_tcp_rx's
+# eight and struct gcl_tcp_conn_ext
+TCPRX_SF_RULE2, TCPRX_SF_TXWAKE, TCPRX_SF_FASTRTX, TCPRX_SF_DROPPED = 0x10, 0x20, 0x40, 0x80
+TCPX_TXWAKE, TCPX_FASTRTX = 0x01, 0x02
+TCPRXFC_RULE2, TCPRXFC_TXWAKES, TCPRXFC_FASTRTX, TCPRXFC_DUPACKS, TCPRXFC_DROPPED, TCPRXFC_NR = 8, 9, 10, 11, 12, 13
+TCP_CONN_EXT_DTYPE = np.dtype([("nrule2", "<u4"), ("ndropped", "<u4"), ("fast_rtx_ack", "<u4"),
+                               ("rep_acks", "u1"), ("xflags", "u1"), ("pad", "u1", (2,))])
 # gcl_tcp_tick / gcl_tcp_rx_acks: the timer flags, the action bits (bits 0..6 are also the first
 # counter slots), the segment kinds, the counters, the caps, the TCP states the sweep tests,
 # struct gcl_tcp_tmr, struct gcl_tcp_tmr_out and struct gcl_tcp_addr
@@ -402,6 +409,10 @@ class GclTcprxIn(ctypes.Structure):
                 ("conn", ctypes.c_void_p), ("nconn", ctypes.c_uint32), ("blocks", ctypes.c_uint32)]
 
 
+class GclTcprxfIn(ctypes.Structure):
+    _fields_ = GclTcprxIn._fields_ + [("rep_acks", ctypes.c_void_p)]
+
+
 TCPRX_ENTRY_FIELDS = ("verdict", "sflags", "rcv_nxt_after", "copy_len", "dst_off")
 TCPRX_OUT_FIELDS = TCPRX_ENTRY_FIELDS + ("out_conn", "conn_off")
 
@@ -460,6 +471,7 @@ assert ctypes.sizeof(GclTickIn) == 64 and ctypes.sizeof(GclTickOut) == 56 and ct
 assert ctypes.sizeof(GclCtlsegOut) == 48 and TCP_TMR_DTYPE.itemsize == 64 and TCP_TMR_OUT_DTYPE.itemsize == 32
 assert TCP_ADDR_DTYPE.itemsize == 16
 assert ctypes.sizeof(GclTcprxIn) == 56 and ctypes.sizeof(GclTcprxOut) == 56
+assert ctypes.sizeof(GclTcprxfIn) == 64 and TCP_CONN_EXT_DTYPE.itemsize == 16
 assert TCP_CONN_DTYPE.itemsize == 48 and TCP_CONN_OUT_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclSegIn) == 64 and ctypes.sizeof(GclSegOut) == 104 and SEG_SEND_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclTxhIn) == 88 and ctypes.sizeof(GclTxhNet) == 20 and TXH_DESC_DTYPE.itemsize == 32
@@ -566,6 +578,11 @@ def _load():
                              ctypes.POINTER(GclTcprxOut), vp, vp, ctypes.c_size_t, vp]),
         "gcl_tcp_rx_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxIn),
                                   ctypes.POINTER(GclTcprxOut), vp]),
+        "gcl_tcp_rx_full_workspace": (i32, [u64, u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_rx_full": (i32, [vp, ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxfIn),
+                                  ctypes.POINTER(GclTcprxOut), vp, vp, vp, ctypes.c_size_t, vp]),
+        "gcl_tcp_rx_full_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxfIn),
+                                       ctypes.POINTER(GclTcprxOut), vp, vp]),
         "gcl_tcp_tick_workspace": (i32, [u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
         "gcl_tcp_tick": (i32, [vp, ctypes.POINTER(GclTickIn), ctypes.POINTER(GclTickOut), vp, vp,
                                ctypes.c_size_t, vp]),
@@ -1120,6 +1137,55 @@ def tcp_rx_workspace(m, nconn, blocks=0):
     """gcl_tcp_rx_workspace: bytes of device scratch a call over @m entries and @nconn connections takes."""
     need = ctypes.c_size_t()
     _check(lib.gcl_tcp_rx_workspace(m, nconn, blocks, ctypes.byref(need)), "gcl_tcp_rx_workspace")
+    return need.value
+
+
+def _tcprxf_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status, conn, nconn,
+                    align, blocks, out, counts, rep_acks):
+    """The three structs of gcl_tcp_rx_full / gcl_tcp_rx_full_host, sizes
+    checked; @out maps TCPRX_OUT_FIELDS and "out_ext" to buffers."""
+    if counts is not None and _nbytes(counts) < 8 * TCPRXFC_NR:
+        raise ValueError("counts buffer too small")
+    if rep_acks is not None and _nbytes(rep_acks) < nconn:
+        raise ValueError("rep_acks too small")
+    if out["out_ext"] is not None and _nbytes(out["out_ext"]) < 16 * nconn:
+        raise ValueError("out_ext too small")
+    b, rin, rout = _tcprx_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status,
+                                  conn, nconn, align, blocks, out, None)
+    fin = GclTcprxfIn(size=ctypes.sizeof(GclTcprxfIn), align=align, order=rin.order, m=m, sock=rin.sock,
+                      l4_status=rin.l4_status, conn=rin.conn, nconn=nconn, blocks=blocks,
+                      rep_acks=_ptr(rep_acks))
+    return b, fin, rout
+
+
+def tcp_rx_full_host(frames, pkt_len, sock, conn, stride=0, offs=None, n=None, frames_len=None, order=None,
+                     m=None, l4_status=None, nconn=None, align=0, blocks=0, rep_acks=None, out=None,
+                     counts=None):
+    """gcl_tcp_rx_full_host: the rule of Classifier.tcp_rx_full on the CPU over
+    numpy arrays: tcp_rx_host's arguments, @rep_acks (u8[nconn], None: zeros)
+    and in @out also "out_ext" (TCP_CONN_EXT_DTYPE[nconn]).  @counts is a
+    u64[TCPRXFC_NR], accumulated.  Returns the dict."""
+    n = len(pkt_len) if n is None else n
+    m = _pay_m(n, m, order)
+    nconn = len(conn) if nconn is None else nconn
+    out = dict(out or {})
+    for f, dt, k in (("verdict", np.uint8, m), ("sflags", np.uint8, m), ("rcv_nxt_after", np.uint32, m),
+                     ("copy_len", np.uint16, m), ("dst_off", np.uint64, m),
+                     ("out_conn", TCP_CONN_OUT_DTYPE, nconn), ("conn_off", np.uint64, nconn + 1),
+                     ("out_ext", TCP_CONN_EXT_DTYPE, nconn)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    b, fin, rout = _tcprxf_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status,
+                                   conn, nconn, align, blocks, out, counts, rep_acks)
+    _check(lib.gcl_tcp_rx_full_host(ctypes.byref(b), ctypes.byref(fin), ctypes.byref(rout), _ptr(out["out_ext"]),
+                                    _ptr(counts)), "gcl_tcp_rx_full_host")
+    return out
+
+
+def tcp_rx_full_workspace(m, nconn, blocks=0):
+    """gcl_tcp_rx_full_workspace: bytes of device scratch a call over @m entries and @nconn connections takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_rx_full_workspace(m, nconn, blocks, ctypes.byref(need)), "gcl_tcp_rx_full_workspace")
     return need.value
 
 
@@ -1872,6 +1938,42 @@ class Classifier:
                 ws = self._tcprx_ws = torch.empty(need, dtype=torch.uint8, device=out["conn_off"].device)
         _check(lib.gcl_tcp_rx(self._ctx, ctypes.byref(b), ctypes.byref(rin), ctypes.byref(rout),
                               _ptr(counts), _ptr(ws), _nbytes(ws), stream), "gcl_tcp_rx")
+        return out
+
+    def tcp_rx_full(self, frames, n, pkt_len, sock, conn, nconn, stride=0, offs=None, frames_len=None,
+                    order=None, m=None, l4_status=None, align=0, blocks=0, rep_acks=None, out=None,
+                    counts=None, workspace=None, stream=None):
+        """gcl_tcp_rx_full: tcp_rx_conn with the established part of its slow
+        path for one runtime's list on the GPU, asynchronous.  The arguments
+        are tcp_rx's; @rep_acks is a device uint8[nconn] (None: zeros), @out
+        also holds "out_ext" (uint8[nconn, 16], TCP_CONN_EXT_DTYPE records) and
+        @counts is a device u64[TCPRXFC_NR], accumulated.  Returns the dict:
+        verdict, sflags and rcv_nxt_after are tcp_rx_acks' inputs, copy_len and
+        dst_off copy_batch's, out_conn's snd_una and out_ext's xflags what
+        tcp_txq's conn and want are made of."""
+        import torch
+        m = _pay_m(n, m, order)
+        dev = frames.device if hasattr(frames, "device") else None
+        out = dict(out or {})
+        mm = max(m, 1)
+        for f, dt, shape in (("verdict", torch.uint8, (mm,)), ("sflags", torch.uint8, (mm,)),
+                             ("rcv_nxt_after", torch.int32, (mm,)), ("copy_len", torch.int16, (mm,)),
+                             ("dst_off", torch.int64, (mm,)), ("out_conn", torch.uint8, (max(nconn, 1), 48)),
+                             ("conn_off", torch.int64, (nconn + 1,)),
+                             ("out_ext", torch.uint8, (max(nconn, 1), 16))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        b, fin, rout = _tcprxf_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock,
+                                       l4_status, conn, nconn, align, blocks, out, counts, rep_acks)
+        ws = workspace
+        if ws is None:
+            need = tcp_rx_full_workspace(m, nconn, blocks)
+            ws = getattr(self, "_tcprx_ws", None)
+            if ws is None or ws.numel() < need or ws.device != out["conn_off"].device:
+                ws = self._tcprx_ws = torch.empty(need, dtype=torch.uint8, device=out["conn_off"].device)
+        _check(lib.gcl_tcp_rx_full(self._ctx, ctypes.byref(b), ctypes.byref(fin), ctypes.byref(rout),
+                                   _ptr(out["out_ext"]), _ptr(counts), _ptr(ws), _nbytes(ws), stream),
+               "gcl_tcp_rx_full")
         return out
 
     def _ctlseg_device_arrays(self, out, seg_cap, dev):

@@ -247,6 +247,19 @@ int gcl_tcp_rx_host(const struct gcl_batch *b, const struct gcl_tcprx_in *in,
                     const struct gcl_tcprx_out *out, uint64_t *counts);
 
 /*
+ * gcl_tcp_rx_full_host - the rule of gcl_tcp_rx_full (gclassify.h) on the CPU
+ * over host pointers: gcl_tcp_rx_host's walk with the fast path and the
+ * established part of __tcp_rx_conn (runtime/net/tcp_in.c:352-611), the rule
+ * the kernel shares (csrc/gcl_tcprxf.h).  Every connection's live words are
+ * kept in out_conn and out_ext; no grouping and no workspace.  @counts is a
+ * host u64[GCL_TCPRXFC_NR], ACCUMULATED, may be NULL.  The same outputs byte
+ * for byte, the same counts and the same guarantee.  0, or -EINVAL for what
+ * gcl_tcp_rx_full refuses (the ctx and the workspace apart).
+ */
+int gcl_tcp_rx_full_host(const struct gcl_batch *b, const struct gcl_tcprxf_in *in,
+                         const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext, uint64_t *counts);
+
+/*
  * gcl_tcp_tick_host, gcl_tcp_rx_acks_host - the rules of gcl_tcp_tick and
  * gcl_tcp_rx_acks (gclassify.h) on the CPU over host pointers, for the sweeps
  * and lists the GPU did not see: tcp_worker's walk with tcp_handle_timeouts and

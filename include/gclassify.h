@@ -1828,6 +1828,128 @@ int gcl_tcp_rx(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct gcl_
                void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /*
+ * TCP receive with the established slow path: gcl_tcp_rx_full stands where
+ * gcl_tcp_rx stands and takes, besides the fast path, the part of
+ * __tcp_rx_conn (runtime/net/tcp_in.c:352-611) that a connection in
+ * ESTABLISHED with an empty out-of-order queue needs: acceptability, the ACK
+ * and window update, the sender wake-up, duplicate-ACK counting and in-order
+ * text under the slow rule's own wake and delayed-ACK steps.  gcl_tcp_rx stops
+ * a connection at its first pure ACK (len == 0 is slow, :222), so it does
+ * nothing for a connection that mostly sends; this call keeps going.
+ *
+ *   gcl_l4_payload -> gcl_tcp_rx_full -> gcl_copy_batch
+ *                  -> gcl_tcp_rx_acks -> gcl_tx_hdr
+ *                  -> gcl_tcp_txq (snd_una from out_conn, GCL_TXQ_W_FAST for a
+ *                     connection whose out_ext has GCL_TCPX_FASTRTX)
+ *
+ * Lists, segments, one runtime per call, arithmetic (mod 2^32, wraps_*; win
+ * shifted by snd_wscale & 31; snd_nxt the snapshot's) and the lines NA, NOCONN
+ * and DROP are gcl_tcp_rx's.  Then, for one segment of connection c, the
+ * entries of a connection in list order:
+ *  1. The connection has not stopped and gcl_tcp_rx's rule says FAST: the fast
+ *     path as there; its ACKED or WND also sets rep_acks = 0.
+ *  2. Otherwise the segment is __tcp_rx_conn's.  It STOPS the connection
+ *     (verdict SLOW, the state frozen as it stood before the segment,
+ *     first_slow set, every later segment SLOW, as in gcl_tcp_rx) when the
+ *     connection has stopped already, is not GCL_TCPC_ELIGIBLE, the segment
+ *     carries FIN, RST, URG or SYN, or it is acceptable text (len > 0,
+ *     is_acceptable) with seq != rcv_nxt: the out-of-order queue or a head
+ *     clip.
+ *  3. Every other segment is HANDLED (sflags RULE2), in the reference's order:
+ *     is_acceptable (:27-51) false: do_ack, done.
+ *     no ACK flag: done.
+ *     snd_was_full = wraps_lte(snd_una + snd_wnd, snd_nxt).
+ *     if wraps_lte(snd_una, ack) and wraps_lte(ack, snd_nxt):
+ *       snd_una != ack: snd_una = ack (ACKED); else ack_same.
+ *       if wraps_lt(snd_wl1, seq) or (snd_wl1 == seq and wraps_lte(snd_wl2, ack)),
+ *       and (!ack_same or snd_wnd <= win): wnd_updated when snd_wnd != win or
+ *       snd_wl2 != ack; snd_wnd = win, snd_wl1 = seq, snd_wl2 = ack (WND).
+ *     else if wraps_gt(ack, snd_nxt): do_ack, done.
+ *     snd_was_full and no longer full: TXWAKE.
+ *     if ack_same and snd_una != snd_nxt and len == 0 and !wnd_updated:
+ *       rep_acks++ (the reference's int; counted in DUPACKS); at 3 or more
+ *       FASTRTX, fast_rtx_ack = ack, rep_acks = 0.
+ *     else if snd_una == ack: rep_acks = 0.
+ *     len > 0 (the text starts at rcv_nxt and rcv_wnd > 0): wake on PSH or
+ *       GCL_TCPC_RXQ; the tail is clipped to rcv_wnd; rcv_nxt and rcv_wnd move
+ *       by the accepted bytes; GCL_TCPC_RXQ is set; wake when rcv_wnd reached
+ *       0 (WAKE); ++acks_delayed_cnt >= 2: do_ack, else if ACK_DELAYED is
+ *       clear it is set (TIMER_ARMED).  do_drop = false.
+ *     done: do_ack clears ACK_DELAYED and the counter (ACK_NOW), so a segment
+ *       that is not acceptable cancels a pending delayed ACK; do_drop as it
+ *       stands (DROPPED): every handled segment that left no text.
+ *     GCL_TCPO_REP_ACKS_RESET is set whenever some segment set rep_acks = 0.
+ *
+ * Per-entry outputs are gcl_tcprx_out's arrays: verdict GCL_TCPRX_FAST for
+ * every handled segment, by either rule, so that gcl_tcp_rx_acks takes
+ * verdict, sflags and rcv_nxt_after of this call unchanged; rcv_nxt_after =
+ * rcv_nxt after the segment for every handled one (rcv_wnd falls only by
+ * accepted bytes, so the window follows from it), 0 otherwise; sflags with
+ * four more bits; copy_len the accepted byte count (0 for pure ACKs and drops,
+ * the clipped length after a tail clip); dst_off = conn_off[c] + (seq -
+ * conn[c].rcv_nxt) where copy_len > 0, else 0.  Accepted text always starts at
+ * rcv_nxt, so fast_bytes, conn_off and the layout are gcl_tcp_rx's.
+ * out_conn[c] as there, nfast counting the handled segments; out_ext[c] adds
+ * nrule2 and ndropped (handled under rule 2; DROPPED among them),
+ * fast_rtx_ack (the ack of the last FASTRTX, for fast_retransmit_last_ack; 0
+ * without one), rep_acks as it stands after the list and xflags.  A
+ * connection with no segment in the list gets its input back.
+ *
+ * @in is gcl_tcprx_in's fields with its own size and rep_acks: an optional
+ * device u8[nconn], c->rep_acks per connection, NULL meaning zeros.  @counts
+ * is a device u64[GCL_TCPRXFC_NR], ACCUMULATED, may be NULL: the first eight
+ * slots as gcl_tcp_rx (FAST: handled), then RULE2, TXWAKES, FASTRTX, DUPACKS
+ * (rep_acks++ events) and DROPPED.  The bounds guarantee is gcl_tcp_rx's, with
+ * rep_acks[0, nconn) among the reads and out_ext[0, nconn) among the writes.
+ *
+ * What stays with the runtime: every SLOW segment and what follows it (the
+ * out-of-order queue, head-clipped text, FIN / RST / URG / SYN, every other
+ * state), tcp_timer_update at done, tcp_conn_ack's frees (ACKED), the
+ * wake-ups (WAKE; TXWAKE: POLLOUT and waitq_release of tx_wq), the fast
+ * retransmit itself (FASTRTX: do_fast_retransmit with tx_exclusive, else
+ * tcp_tx_fast_retransmit_start, or GCL_TXQ_W_FAST for gcl_tcp_txq), freeing
+ * the mbufs (DROPPED), sending the ACKs, and the lock.
+ *
+ * gcl_tcp_rx_full_workspace, gcl_tcp_rx_full - as gcl_tcp_rx_workspace and
+ *   gcl_tcp_rx: asynchronous, launches ordered by the stream alone, no block
+ *   waits for another, no atomic's order decides a result, no allocation, no
+ *   host synchronisation, a workspace that need not be zeroed.  -EINVAL for
+ *   what gcl_tcp_rx refuses, and with nconn > 0 for an out_ext that is NULL or
+ *   not 16-B aligned.
+ */
+#define GCL_TCPRX_SF_RULE2   0x10  /* went through __tcp_rx_conn */
+#define GCL_TCPRX_SF_TXWAKE  0x20  /* POLLOUT + waitq_release of tx_wq */
+#define GCL_TCPRX_SF_FASTRTX 0x40  /* rep_acks reached TCP_FAST_RETRANSMIT_THRESH */
+#define GCL_TCPRX_SF_DROPPED 0x80  /* do_drop: the mbuf is freed */
+/* gcl_tcp_conn_ext.xflags */
+#define GCL_TCPX_TXWAKE  0x01  /* some segment had TXWAKE */
+#define GCL_TCPX_FASTRTX 0x02  /* some segment had FASTRTX */
+enum { GCL_TCPRXFC_RULE2 = 8, GCL_TCPRXFC_TXWAKES, GCL_TCPRXFC_FASTRTX, GCL_TCPRXFC_DUPACKS,
+       GCL_TCPRXFC_DROPPED, GCL_TCPRXFC_NR = 13 };
+struct gcl_tcp_conn_ext {  /* 16 B, 16-B aligned */
+	uint32_t nrule2, ndropped;
+	uint32_t fast_rtx_ack;
+	uint8_t  rep_acks;
+	uint8_t  xflags;       /* GCL_TCPX_* */
+	uint8_t  pad[2];       /* written 0 */
+};
+struct gcl_tcprxf_in {
+	uint32_t size, align;            /* sizeof(struct gcl_tcprxf_in) */
+	const uint32_t *order;
+	uint64_t m;
+	const uint32_t *sock;
+	const uint8_t  *l4_status;
+	const struct gcl_tcp_conn *conn;
+	uint32_t nconn;
+	uint32_t blocks;
+	const uint8_t  *rep_acks;        /* optional u8[nconn]; NULL: zeros */
+};
+int gcl_tcp_rx_full_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, size_t *bytes);
+int gcl_tcp_rx_full(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct gcl_tcprxf_in *in,
+                    const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext, uint64_t *counts,
+                    void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/*
  * TCP control segments: the timer sweep, and the ACKs of a gcl_tcp_rx call.
  * Both chains end where TCP asks for a segment that carries no data.  In the
  * reference that is per-connection work on a core: tcp_worker
@@ -2149,7 +2271,8 @@ int gcl_tcp_rx_acks(struct gcl_ctx *ctx, const struct gcl_rxack_in *in, const st
  * each walked; state[e] of an entry two of them share is that of either.
  *
  * What stays with the runtime: the frees themselves, tcp_write_finish's
- * wake-ups, do_fast_retransmit's bookkeeping (the caller decides W_FAST),
+ * wake-ups, do_fast_retransmit's bookkeeping (the caller decides W_FAST;
+ * gcl_tcp_rx_full's GCL_TCPX_FASTRTX says when),
  * writing the timestamps and seg_seq back, and the lock.
  *
  * gcl_tcp_txq_workspace - bytes of device scratch a call takes: 4 per block
