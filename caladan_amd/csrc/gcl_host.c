@@ -4,6 +4,7 @@
  */
 #include <errno.h>
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/gcl_host.h"
@@ -12,6 +13,7 @@
 #include "gcl_seg.h"
 #include "gcl_tcprx.h"
 #include "gcl_tcprxf.h"
+#include "gcl_tcprxo.h"
 #include "gcl_tcptmr.h"
 #include "gcl_txq.h"
 #include "gcl_txh.h"
@@ -829,6 +831,330 @@ int gcl_tcp_rx_full_host(const struct gcl_batch *b, const struct gcl_tcprxf_in *
 		}
 	if (counts)
 		for (int k = 0; k < GCL_TCPRXFC_NR; k++)
+			counts[k] += c[k];
+	return 0;
+}
+
+/* a live queue entry of gcl_tcp_rx_ooo_host: @fl is flags | src << 16, @idx the index into q or the list */
+struct tcprxo_ent {
+	uint32_t seq, end, fl, idx;
+};
+
+struct tcprxo_cnt {
+	uint32_t ooo, queued, drained, freed, headclip, held;
+};
+
+/* what a queue entry that leaves the queue gets: @t is GCL_TCPRXO_APPEND or GCL_TCPRXO_FREE */
+static void tcprxo_fate(const struct gcl_tcprx_out *out, const struct gcl_tcprxo_out *oo,
+                        const struct tcprxo_ent *e, uint32_t t, uint32_t head, uint32_t ln, uint32_t rel)
+{
+	if (e->fl >> 16) {
+		const uint32_t j = e->idx;
+
+		out->copy_len[j] = (uint16_t)ln;
+		out->dst_off[j] = ln ? rel : 0;
+		oo->oflags[j] = (uint8_t)(GCL_OOOF_OOO | GCL_OOOF_QUEUED | (head ? GCL_OOOF_HEADCLIP : 0) |
+		                          (t == GCL_TCPRXO_APPEND ? GCL_OOOF_LATE_DRAINED : GCL_OOOF_LATE_FREED));
+		oo->skip[j] = (uint16_t)head;
+	} else {
+		const uint32_t i = e->idx;
+
+		oo->qin_state[i] = t == GCL_TCPRXO_APPEND ? GCL_OOOQ_DRAINED : GCL_OOOQ_FREED;
+		oo->qin_skip[i] = gcl_tcprxo_u16(head);
+		oo->qin_len[i] = gcl_tcprxo_u16(ln);
+		oo->qin_dst_off[i] = ln ? rel : 0;
+	}
+}
+
+/* tcp_in.c:124-135 over the live queue: the insert position, or GCL_TCPRXO_REJECT */
+static uint32_t tcprxo_find(const struct tcprxo_ent *Q, uint32_t qn, uint32_t seq, uint32_t end)
+{
+	uint64_t ends = 0, seqs = 0;
+
+	for (uint32_t i = 0; i < qn; i++) {
+		const uint32_t t = gcl_tcprxo_pos_test(seq, end, Q[i].seq, Q[i].end);
+
+		ends |= (uint64_t)(t & GCL_TCPRXO_POS_END ? 1 : 0) << i;
+		seqs |= (uint64_t)(t & GCL_TCPRXO_POS_SEQ ? 1 : 0) << i;
+	}
+	return gcl_tcprxo_pos(ends, seqs);
+}
+
+/* The rule of gcl_tcp_rx_ooo (gclassify.h) on the CPU: the list is threaded
+ * per connection (next[], in list order), then every connection walks its
+ * segments with its queue in a local array of GCL_TCPOOO_CAP entries, composed
+ * of the pieces of gcl_tcprxo.h as the GPU walk composes them. */
+int gcl_tcp_rx_ooo_host(const struct gcl_batch *b, const struct gcl_tcprxo_in *oin,
+                        const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext,
+                        const struct gcl_tcprxo_out *oo, uint64_t *counts)
+{
+	uint64_t c[GCL_TCPRXOC_NR] = {0}, at = 0;
+
+	if (!b || !oin || !out || !oo || oin->size != sizeof(*oin))
+		return -EINVAL;
+	const struct gcl_tcprx_in rin = {sizeof(rin), oin->align, oin->order, oin->m, oin->sock, oin->l4_status,
+	                                 oin->conn, oin->nconn, oin->blocks};
+	const struct gcl_tcprx_in *in = &rin;
+	const uint32_t nq = oin->nq;
+
+	if (!gcl_pay_align_ok(in->align) ||
+	    (!in->order && in->m != b->n) || in->m > (1ull << 31) || in->nconn > GCL_TCPRX_MAX_CONN ||
+	    in->blocks > GCL_TCPRX_MAX_BLOCKS || !in->sock || !out->conn_off || nq > (1u << 31) || !oo->qout_off ||
+	    !oo->totals)
+		return -EINVAL;
+	if (in->nconn && (!in->conn || !out->out_conn || !out_ext))
+		return -EINVAL;
+	if (in->m && (!out->verdict || !out->sflags || !out->rcv_nxt_after || !out->copy_len || !out->dst_off ||
+	              !oo->oflags || !oo->skip))
+		return -EINVAL;
+	if (nq && (!oin->q || !oo->qin_state || !oo->qin_skip || !oo->qin_len || !oo->qin_dst_off))
+		return -EINVAL;
+	if (oin->q_out_cap && !oo->qout)
+		return -EINVAL;
+	if (((uintptr_t)in->order & 3) || ((uintptr_t)in->sock & 3) || ((uintptr_t)in->conn & 15) ||
+	    ((uintptr_t)out->rcv_nxt_after & 3) || ((uintptr_t)out->copy_len & 1) || ((uintptr_t)out->dst_off & 7) ||
+	    ((uintptr_t)out->out_conn & 15) || ((uintptr_t)out->conn_off & 7) || ((uintptr_t)counts & 7) ||
+	    ((uintptr_t)out_ext & 15) || ((uintptr_t)oin->q_off & 3) || ((uintptr_t)oin->q & 15) ||
+	    ((uintptr_t)oo->skip & 1) || ((uintptr_t)oo->qin_skip & 1) || ((uintptr_t)oo->qin_len & 1) ||
+	    ((uintptr_t)oo->qin_dst_off & 7) || ((uintptr_t)oo->qout_off & 3) || ((uintptr_t)oo->qout & 15) ||
+	    ((uintptr_t)oo->totals & 7))
+		return -EINVAL;
+	if (in->m && (!b->frames || b->frames_len == UINT64_MAX || b->n > (1ull << 40) ||
+	              (!b->offs && (b->stride < 16 || (b->stride & 15) || b->stride > (1u << 20))) ||
+	              !b->pkt_len || ((uintptr_t)b->pkt_len & 1)))
+		return -EINVAL;
+	const uint32_t amask = in->align ? in->align - 1 : 0;
+	/* first[k], last[k] and next[j]: connection k's segments in list order */
+	uint32_t *link = malloc(4 * ((size_t)in->m + 2 * (size_t)in->nconn) + 4);
+
+	if (!link)
+		return -ENOMEM;
+	uint32_t *first = link, *last = link + in->nconn, *next = link + 2 * (size_t)in->nconn;
+
+	for (uint32_t k = 0; k < in->nconn; k++)
+		first[k] = last[k] = GCL_TCPRX_NONE;
+	for (uint32_t i = 0; i < nq; i++) {
+		oo->qin_state[i] = GCL_OOOQ_UNTOUCHED;
+		oo->qin_skip[i] = 0;
+		oo->qin_len[i] = 0;
+		oo->qin_dst_off[i] = 0;
+	}
+	for (uint64_t j = 0; j < in->m; j++) {
+		struct gcl_tcprx_seg s = {0, 0, 0, 0, 0};
+		const uint32_t k = tcprx_entry(b, in, j, &s);
+		const uint32_t verdict = k == GCL_TCPRX_NONE ? GCL_TCPRX_NA : k >= in->nconn ? GCL_TCPRX_NOCONN :
+		                         s.len > in->conn[k].rcv_mss ? GCL_TCPRX_DROP : GCL_TCPRX_FAST;
+
+		out->verdict[j] = (uint8_t)verdict;
+		out->sflags[j] = 0;
+		out->rcv_nxt_after[j] = 0;
+		out->copy_len[j] = 0;
+		out->dst_off[j] = 0;
+		oo->oflags[j] = 0;
+		oo->skip[j] = 0;
+		next[j] = GCL_TCPRX_NONE;
+		if (verdict != GCL_TCPRX_FAST) {
+			c[verdict]++;
+			continue;
+		}
+		if (first[k] == GCL_TCPRX_NONE)
+			first[k] = (uint32_t)j;
+		else
+			next[last[k]] = (uint32_t)j;
+		last[k] = (uint32_t)j;
+	}
+	for (uint32_t k = 0; k < in->nconn; k++) {
+		struct gcl_tcp_conn cn = in->conn[k];
+		struct gcl_tcp_conn_out *o = &out->out_conn[k];
+		struct gcl_tcp_conn_ext *e = &out_ext[k];
+		struct gcl_tcprxf_live x = {gcl_tcprx_live_of(&cn), oin->rep_acks ? oin->rep_acks[k] : 0, 0, 0};
+		struct tcprxo_ent Q[GCL_TCPOOO_CAP];
+		struct tcprxo_cnt n = {0, 0, 0, 0, 0, 0};
+		uint32_t qs = 0, qe = 0, qn = 0, nfast = 0, nslow = 0, nacks = 0, nrule2 = 0, ndropped = 0;
+		uint32_t first_slow = GCL_TCPRX_NONE;
+
+		if (oin->q_off) {
+			qs = oin->q_off[k] < nq ? oin->q_off[k] : nq;
+			qe = oin->q_off[k + 1] < nq ? oin->q_off[k + 1] : nq;
+			if (qe < qs)
+				qe = qs;
+		}
+		int taken = gcl_tcprxo_state_ok(cn.flags) && qe - qs <= GCL_TCPOOO_CAP;
+
+		for (uint32_t i = qs; taken && i < qe; i++) {
+			Q[i - qs] = (struct tcprxo_ent){oin->q[i].seq, oin->q[i].end, oin->q[i].flags, i};
+			if (oin->q[i].flags & GCL_TCPRX_FIN)
+				taken = 0;
+		}
+		if (taken) {
+			qn = qe - qs;
+			cn.flags |= GCL_TCPC_ELIGIBLE;
+		} else if (qe != qs) {
+			x.xflags |= GCL_TCPX_QSKIP;
+		}
+		for (uint32_t j = first[k]; j != GCL_TCPRX_NONE; j = next[j]) {
+			struct gcl_tcprx_seg s = {0, 0, 0, 0, 0};
+			struct gcl_tcprxo_mid mid;
+			uint32_t sf = 0, len = 0, head = 0, of = 0;
+			const uint32_t rel = x.l.rcv_nxt - in->conn[k].rcv_nxt; /* where an in-order piece lands */
+			int stop = (x.l.flags & GCL_TCPO_STOPPED) != 0 || !taken;
+
+			(void)tcprx_entry(b, in, j, &s);
+			if (!stop && qn == GCL_TCPOOO_CAP && gcl_tcprxo_reaches_ooo(&cn, &x.l, &s))
+				stop = tcprxo_find(Q, qn, s.seq, s.seq + s.len) != GCL_TCPRXO_REJECT;
+			if (!stop) {
+				const uint32_t st = gcl_tcprxo_head(&cn, &x, &s, qn, &mid, &len);
+
+				if (st == GCL_TCPRXO_STOP) {
+					stop = 1;
+				} else if (st == GCL_TCPRXO_FASTED) {
+					sf = mid.sf;
+				} else {
+					if (st == GCL_TCPRXO_TEXT) {
+						int used = 1, wake = 0;
+
+						if (gcl_tcprxo_in_order(&x.l, s.seq)) {
+							wake = gcl_tcprxo_in_order_wake(&x.l, s.flags);
+							gcl_tcprxo_append(&x.l, s.seq, s.seq + s.len, &head, &len);
+							if (head) {
+								of |= GCL_OOOF_HEADCLIP;
+								n.headclip++;
+							}
+						} else {
+							const uint32_t pos = tcprxo_find(Q, qn, s.seq, s.seq + s.len);
+
+							of |= GCL_OOOF_OOO;
+							n.ooo++;
+							if (pos == GCL_TCPRXO_REJECT) {
+								used = 0;
+							} else {
+								memmove(&Q[pos + 1], &Q[pos], (qn - pos) * sizeof(Q[0]));
+								Q[pos] = (struct tcprxo_ent){s.seq, s.seq + s.len, s.flags | 1u << 16, j};
+								qn++;
+								of |= GCL_OOOF_QUEUED;
+								n.queued++;
+							}
+						}
+						while (used && qn) {
+							const uint32_t t = gcl_tcprxo_drain_test(Q[0].seq, Q[0].end, x.l.rcv_nxt);
+							uint32_t h = 0, ln = 0;
+							const uint32_t r = x.l.rcv_nxt - in->conn[k].rcv_nxt;
+
+							if (t == GCL_TCPRXO_BREAK)
+								break;
+							if (t == GCL_TCPRXO_APPEND) {
+								wake = 1;
+								gcl_tcprxo_append(&x.l, Q[0].seq, Q[0].end, &h, &ln);
+								n.headclip += h != 0;
+								n.drained++;
+							} else {
+								n.freed++;
+							}
+							tcprxo_fate(out, oo, &Q[0], t, h, ln, r);
+							memmove(&Q[0], &Q[1], (qn - 1) * sizeof(Q[0]));
+							qn--;
+						}
+						gcl_tcprxo_text_tail(&x.l, &mid, used, wake, qn);
+					}
+					sf = gcl_tcprxo_done(&x.l, &mid);
+				}
+			}
+			if (stop) {
+				if (!(x.l.flags & GCL_TCPO_STOPPED))
+					first_slow = j;
+				x.l.flags |= GCL_TCPO_STOPPED;
+				nslow++;
+				out->verdict[j] = GCL_TCPRX_SLOW;
+				c[GCL_TCPRX_SLOW]++;
+				continue;
+			}
+			nfast++;
+			nacks += (sf & GCL_TCPRX_SF_ACK_NOW) != 0;
+			nrule2 += (sf & GCL_TCPRX_SF_RULE2) != 0;
+			ndropped += (sf & GCL_TCPRX_SF_DROPPED) != 0;
+			c[GCL_TCPRX_FAST]++;
+			c[GCL_TCPRXC_WAKES] += (sf & GCL_TCPRX_SF_WAKE) != 0;
+			c[GCL_TCPRXFC_TXWAKES] += (sf & GCL_TCPRX_SF_TXWAKE) != 0;
+			c[GCL_TCPRXFC_FASTRTX] += (sf & GCL_TCPRX_SF_FASTRTX) != 0;
+			c[GCL_TCPRXFC_DUPACKS] += (sf & GCL_TCPRXF_EV_DUPACK) != 0;
+			out->sflags[j] = (uint8_t)sf;
+			out->rcv_nxt_after[j] = x.l.rcv_nxt;
+			if (!(of & GCL_OOOF_QUEUED)) { /* a queued entry gets these with its fate */
+				out->copy_len[j] = (uint16_t)len;
+				out->dst_off[j] = len ? rel : 0;
+				oo->oflags[j] = (uint8_t)of;
+				oo->skip[j] = (uint16_t)head;
+			}
+		}
+		for (uint32_t i = 0; i < qn; i++) {
+			if (Q[i].fl >> 16) {
+				oo->oflags[Q[i].idx] = GCL_OOOF_OOO | GCL_OOOF_QUEUED | GCL_OOOF_HELD;
+				n.held++;
+			} else {
+				oo->qin_state[Q[i].idx] = GCL_OOOQ_KEPT;
+			}
+			if (at + i < oin->q_out_cap)
+				oo->qout[at + i] = (struct gcl_tcp_ooo_ent){Q[i].seq, Q[i].end,
+				                                            Q[i].fl >> 16 ? Q[i].idx : oin->q[Q[i].idx].ref,
+				                                            (uint16_t)Q[i].fl, (uint16_t)(Q[i].fl >> 16)};
+		}
+		oo->qout_off[k] = (uint32_t)at;
+		at += qn;
+		memset(o, 0, sizeof(*o));
+		o->snd_una = x.l.snd_una;
+		o->snd_wnd = x.l.snd_wnd;
+		o->snd_wl1 = x.l.snd_wl1;
+		o->snd_wl2 = x.l.snd_wl2;
+		o->rcv_nxt = x.l.rcv_nxt;
+		o->rcv_wnd = x.l.rcv_wnd;
+		o->nfast = nfast;
+		o->nslow = nslow;
+		o->nacks = nacks;
+		o->first_slow = first_slow;
+		o->acks_delayed_cnt = (uint8_t)x.l.cnt;
+		o->flags = (uint8_t)x.l.flags;
+		memset(e, 0, sizeof(*e));
+		e->nrule2 = nrule2;
+		e->ndropped = ndropped;
+		e->fast_rtx_ack = x.fast_rtx_ack;
+		e->rep_acks = (uint8_t)x.rep_acks;
+		e->xflags = (uint8_t)x.xflags;
+		c[GCL_TCPRXC_BYTES] += (uint32_t)(x.l.rcv_nxt - in->conn[k].rcv_nxt);
+		c[GCL_TCPRXC_ACKS] += nacks;
+		c[GCL_TCPRXFC_RULE2] += nrule2;
+		c[GCL_TCPRXFC_DROPPED] += ndropped;
+		c[GCL_TCPRXOC_OOO] += n.ooo;
+		c[GCL_TCPRXOC_QUEUED] += n.queued;
+		c[GCL_TCPRXOC_DRAINED] += n.drained;
+		c[GCL_TCPRXOC_FREED] += n.freed;
+		c[GCL_TCPRXOC_HEADCLIP] += n.headclip;
+		c[GCL_TCPRXOC_HELD] += n.held;
+	}
+	oo->qout_off[in->nconn] = (uint32_t)at;
+	oo->totals[0] = at;
+	at = 0;
+	for (uint32_t k = 0; k < in->nconn; k++) {
+		out->conn_off[k] = at;
+		at += gcl_tcprx_pad((uint32_t)(out->out_conn[k].rcv_nxt - in->conn[k].rcv_nxt), amask);
+	}
+	out->conn_off[in->nconn] = at;
+	/* the layout: every accepted piece moves by its connection's offset */
+	for (uint32_t k = 0; k < in->nconn; k++) {
+		for (uint32_t j = first[k]; j != GCL_TCPRX_NONE; j = next[j])
+			if (out->copy_len[j])
+				out->dst_off[j] += out->conn_off[k];
+		if (oin->q_off && gcl_tcprxo_state_ok(in->conn[k].flags)) {
+			const uint32_t qs = oin->q_off[k] < nq ? oin->q_off[k] : nq;
+			const uint32_t qe = oin->q_off[k + 1] < nq ? oin->q_off[k + 1] : nq;
+
+			for (uint32_t i = qs; i < qe && qe - qs <= GCL_TCPOOO_CAP; i++)
+				if (oo->qin_state[i] == GCL_OOOQ_DRAINED && oo->qin_len[i])
+					oo->qin_dst_off[i] += out->conn_off[k];
+		}
+	}
+	free(link);
+	if (counts)
+		for (int k = 0; k < GCL_TCPRXOC_NR; k++)
 			counts[k] += c[k];
 	return 0;
 }

@@ -69,6 +69,7 @@
 #include "gcl_pay.h"
 #include "gcl_tcprx.h"
 #include "gcl_tcprxf.h"
+#include "gcl_tcprxo.h"
 
 namespace gclk {
 
@@ -759,6 +760,422 @@ __global__ void __launch_bounds__(kRxThreads) rxf_counts_kernel(RxfParams p)
 	}
 }
 
+/* ---- gcl_tcp_rx_ooo: its walk with the queue in the wave, the output queues and its counters ---- */
+
+struct RxoParams {
+	RxfParams f;
+	const uint32_t *q_off;  /* [nconn + 1] or NULL */
+	const uint4 *q;         /* struct gcl_tcp_ooo_ent as one 16-B word */
+	uint32_t nq, q_out_cap;
+	uint8_t *oflags;
+	uint16_t *skip;
+	uint8_t *qin_state;
+	uint16_t *qin_skip, *qin_len;
+	unsigned long long *qin_dst_off;
+	uint32_t *qout_off;
+	uint4 *qout;
+	unsigned long long *totals;
+	/* the workspace, behind gcl_tcp_rx_full's */
+	uint4 *ocnt;            /* [nconn]: QUEUED, DRAINED, FREED, HEADCLIP (OOO is xcnt's fourth word) */
+	uint4 *qmeta;           /* [nconn]: the final queue's length | staged << 8 | taken << 9, HELD, and the 64-bit
+	                           mask of the final positions that hold a list entry */
+	uint32_t *qsum;         /* [scan blocks over nconn] */
+	uint4 *stage;           /* [nq + m]: the final queues of the connections that have a run: the entries
+	                           carried over from q in [0, nq), this call's list entries in [nq, nq + m) */
+};
+
+/* the final queue lengths -> qout_off[0, nconn], the total also to totals[0] */
+struct RxQoutIo {
+	typedef uint32_t T;
+	const uint4 *qmeta;
+	uint32_t *qout_off;
+	unsigned long long *totals;
+	uint32_t nconn;
+	__device__ T load(uint32_t c) const { return qmeta[c].x & 0xFFu; }
+	__device__ void store(uint32_t c, T v) const { qout_off[c] = v; }
+	__device__ void store_total(T v) const
+	{
+		qout_off[nconn] = v;
+		totals[0] = v;
+	}
+};
+
+/* connection c's input queue q[*qs, *qe): both below nq whatever q_off holds */
+__device__ __forceinline__ void rxo_range(const RxoParams &p, uint32_t c, uint32_t *qs, uint32_t *qe)
+{
+	*qs = *qe = 0;
+	if (p.q_off) {
+		const uint32_t a = p.q_off[c], b = p.q_off[(size_t)c + 1];
+		*qs = a < p.nq ? a : p.nq;
+		*qe = b < p.nq ? b : p.nq;
+		if (*qe < *qs)
+			*qe = *qs;
+	}
+}
+
+/* a live queue entry, entry i in lane i: @fl is flags | src << 16, @idx the index into q or the list */
+struct RxoEnt {
+	uint32_t seq, end, fl, idx;
+};
+
+/* tcp_in.c:124-135 over the wave: the two tests as ballots, the entry nearest the tail their highest bit */
+__device__ __forceinline__ uint32_t rxo_find(const RxoEnt &e, uint32_t qn, uint32_t lane, uint32_t seq, uint32_t end)
+{
+	const uint32_t t = lane < qn ? gcl_tcprxo_pos_test(seq, end, e.seq, e.end) : 0;
+	const uint64_t ends = __ballot((t & GCL_TCPRXO_POS_END) != 0), seqs = __ballot((t & GCL_TCPRXO_POS_SEQ) != 0);
+
+	return gcl_tcprxo_pos(ends, seqs);
+}
+
+/* what an entry that leaves the queue gets; one lane calls it, and nothing else stores these words */
+__device__ __forceinline__ void rxo_fate(const RxoParams &p, uint32_t fl, uint32_t idx, uint32_t t, uint32_t head,
+                                         uint32_t ln, uint32_t rel)
+{
+	const RxParams &k = p.f.k;
+
+	if (fl >> 16) {
+		k.copy_len[idx] = (uint16_t)ln;
+		k.dst_off[idx] = ln ? rel : 0; /* layout adds conn_off[c] */
+		p.oflags[idx] = (uint8_t)(GCL_OOOF_OOO | GCL_OOOF_QUEUED | (head ? GCL_OOOF_HEADCLIP : 0) |
+		                          (t == GCL_TCPRXO_APPEND ? GCL_OOOF_LATE_DRAINED : GCL_OOOF_LATE_FREED));
+		p.skip[idx] = (uint16_t)head;
+	} else {
+		p.qin_state[idx] = (uint8_t)(t == GCL_TCPRXO_APPEND ? GCL_OOOQ_DRAINED : GCL_OOOQ_FREED);
+		p.qin_skip[idx] = gcl_tcprxo_u16(head);
+		p.qin_len[idx] = gcl_tcprxo_u16(ln);
+		p.qin_dst_off[idx] = ln ? rel : 0;
+	}
+}
+
+/*
+ * One wave per connection, serial and wave-uniform over each chunk as
+ * rxf_walk_kernel, with the connection's out-of-order queue in the wave's
+ * registers: entry i in lane i, @qn entries.  The insert position is two
+ * ballots, an insert or a pop a one-lane shift, the drain reads lane 0.
+ *
+ * Store order.  copy_len, dst_off, oflags and skip of a list entry that was
+ * QUEUED are stored exactly once, when its fate is known: by rxo_fate when it
+ * is popped (in this chunk or a later one) or at the end of the walk when it
+ * is HELD; the chunk's own store skips such an entry.  The same holds for the
+ * qin_* words of an input entry.  So no two stores of this kernel hit one
+ * address and no fence is needed.
+ */
+__global__ void __launch_bounds__(kRxThreads) rxo_walk_kernel(RxoParams p, const uint32_t *sorted)
+{
+	const RxParams &k = p.f.k;
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRxWaves + (threadIdx.x >> 6)));
+
+	if (c >= k.nconn)
+		return;
+	struct gcl_tcp_conn cn;
+	{
+		const uint4 a = k.conn[3 * (size_t)c], b = k.conn[3 * (size_t)c + 1], d = k.conn[3 * (size_t)c + 2];
+		cn.snd_una = a.x; cn.snd_nxt = a.y; cn.snd_wnd = a.z; cn.snd_wl1 = a.w;
+		cn.snd_wl2 = b.x; cn.rcv_nxt = b.y; cn.rcv_wnd = b.z;
+		cn.rcv_mss = (uint16_t)b.w; cn.snd_wscale = (uint8_t)(b.w >> 16); cn.flags = (uint8_t)(b.w >> 24);
+		cn.acks_delayed_cnt = (uint8_t)d.x;
+	}
+	struct gcl_tcprxf_live x;
+	x.l = gcl_tcprx_live_of(&cn);
+	x.rep_acks = p.f.rep_acks ? p.f.rep_acks[c] : 0;
+	x.fast_rtx_ack = 0;
+	x.xflags = 0;
+	const uint32_t rcv0 = cn.rcv_nxt;
+	uint32_t qs, qe;
+	rxo_range(p, c, &qs, &qe);
+	const uint32_t nin = qe - qs;
+	bool taken = gcl_tcprxo_state_ok(cn.flags) && nin <= GCL_TCPOOO_CAP;
+	RxoEnt e = {0, 0, 0, 0};
+	if (taken && lane < nin) {
+		const uint4 w = p.q[qs + lane];
+		e.seq = w.x;
+		e.end = w.y;
+		e.fl = w.w & 0xFFFFu;
+		e.idx = qs + lane;
+	}
+	if (__ballot(taken && lane < nin && (e.fl & GCL_TCPRX_FIN)))
+		taken = false;
+	uint32_t qn = taken ? nin : 0;
+	if (taken)
+		cn.flags |= GCL_TCPC_ELIGIBLE;
+	else if (nin)
+		x.xflags |= GCL_TCPX_QSKIP;
+
+	const uint2 rn = k.run[c];
+	const uint64_t re = rn.y < k.m ? rn.y : k.m;
+	const uint64_t rs = rn.x < re ? rn.x : re;
+	uint32_t nfast = 0, nslow = 0, nacks = 0, wakes = 0, first_slow = GCL_TCPRX_NONE;
+	uint32_t nrule2 = 0, ndropped = 0, ntxw = 0, nfrtx = 0, ndup = 0;
+	uint32_t nooo = 0, nqueued = 0, ndrained = 0, nfreed = 0, nhead = 0;
+
+	for (uint64_t base = rs; base < re; base += 64) { /* uniform */
+		const uint32_t nv = re - base < 64 ? (uint32_t)(re - base) : 64;
+		const bool valid = lane < nv;
+		uint32_t j = valid ? sorted[base + lane] : 0;
+		if (j >= k.m)
+			j = (uint32_t)(k.m - 1);
+		const uint4 rec = valid ? k.rec[j] : make_uint4(0, 0, 0, 0);
+		const bool stopped = (x.l.flags & GCL_TCPO_STOPPED) != 0;
+		uint32_t H = 0, sf_mine = 0, after_mine = 0, copy_mine = 0, head_mine = 0, of_mine = 0, rel_mine = 0;
+
+		if (!stopped && taken) {
+			H = nv;
+			for (uint32_t at = 0; at < nv; at++) { /* uniform */
+				const uint32_t z = rx_lane(rec.z, at);
+				const struct gcl_tcprx_seg s = {rx_lane(rec.x, at), rx_lane(rec.y, at), z & 0xFFFFu,
+				                                rx_lane(rec.w, at), z >> 16};
+				const uint32_t jj = rx_lane(j, at);
+				const uint32_t rel = x.l.rcv_nxt - rcv0; /* where an in-order piece lands */
+				struct gcl_tcprxo_mid mid;
+				uint32_t sf = 0, len = 0, head = 0, of = 0;
+				bool stop = false;
+
+				if (qn == GCL_TCPOOO_CAP && gcl_tcprxo_reaches_ooo(&cn, &x.l, &s))
+					stop = rxo_find(e, qn, lane, s.seq, s.seq + s.len) != GCL_TCPRXO_REJECT;
+				if (!stop) {
+					const uint32_t st = gcl_tcprxo_head(&cn, &x, &s, qn, &mid, &len);
+
+					if (st == GCL_TCPRXO_STOP) {
+						stop = true;
+					} else if (st == GCL_TCPRXO_FASTED) {
+						sf = mid.sf;
+					} else {
+						if (st == GCL_TCPRXO_TEXT) {
+							int used = 1, wake = 0;
+
+							if (gcl_tcprxo_in_order(&x.l, s.seq)) {
+								wake = gcl_tcprxo_in_order_wake(&x.l, s.flags);
+								gcl_tcprxo_append(&x.l, s.seq, s.seq + s.len, &head, &len);
+								if (head) {
+									of |= GCL_OOOF_HEADCLIP;
+									nhead++;
+								}
+							} else {
+								const uint32_t pos = rxo_find(e, qn, lane, s.seq, s.seq + s.len);
+
+								of |= GCL_OOOF_OOO;
+								nooo++;
+								if (pos == GCL_TCPRXO_REJECT) {
+									used = 0;
+								} else { /* the lanes at and above pos move up by one */
+									const RxoEnt u = {(uint32_t)__shfl_up((int)e.seq, 1), (uint32_t)__shfl_up((int)e.end, 1),
+									                  (uint32_t)__shfl_up((int)e.fl, 1), (uint32_t)__shfl_up((int)e.idx, 1)};
+									if (lane > pos)
+										e = u;
+									if (lane == pos) {
+										e.seq = s.seq;
+										e.end = s.seq + s.len;
+										e.fl = s.flags | 1u << 16;
+										e.idx = jj;
+									}
+									qn++;
+									of |= GCL_OOOF_QUEUED;
+									nqueued++;
+								}
+							}
+							while (used && qn) { /* uniform: the drain reads lane 0 */
+								const uint32_t hs = rx_lane(e.seq, 0), he = rx_lane(e.end, 0);
+								const uint32_t hf = rx_lane(e.fl, 0), hi = rx_lane(e.idx, 0);
+								const uint32_t t = gcl_tcprxo_drain_test(hs, he, x.l.rcv_nxt);
+								const uint32_t r = x.l.rcv_nxt - rcv0;
+								uint32_t h = 0, ln = 0;
+
+								if (t == GCL_TCPRXO_BREAK)
+									break;
+								if (t == GCL_TCPRXO_APPEND) {
+									wake = 1;
+									gcl_tcprxo_append(&x.l, hs, he, &h, &ln);
+									nhead += h != 0;
+									ndrained++;
+								} else {
+									nfreed++;
+								}
+								if (lane == 0)
+									rxo_fate(p, hf, hi, t, h, ln, r);
+								e.seq = (uint32_t)__shfl_down((int)e.seq, 1);
+								e.end = (uint32_t)__shfl_down((int)e.end, 1);
+								e.fl = (uint32_t)__shfl_down((int)e.fl, 1);
+								e.idx = (uint32_t)__shfl_down((int)e.idx, 1);
+								qn--;
+							}
+							gcl_tcprxo_text_tail(&x.l, &mid, used, wake, qn);
+						}
+						sf = gcl_tcprxo_done(&x.l, &mid);
+					}
+				}
+				if (stop) {
+					H = at;
+					break;
+				}
+				if (lane == at) {
+					sf_mine = sf;
+					after_mine = x.l.rcv_nxt;
+					copy_mine = len;
+					head_mine = head;
+					of_mine = of;
+					rel_mine = rel;
+				}
+			}
+		}
+		nfast += H;
+		nslow += nv - H;
+		if (H < nv) {
+			if (!stopped)
+				first_slow = rx_lane(j, H);
+			x.l.flags |= GCL_TCPO_STOPPED;
+		}
+		if (H) { /* lanes at and past H hold 0 */
+			nacks += rx_pop(sf_mine & GCL_TCPRX_SF_ACK_NOW);
+			wakes += rx_pop(sf_mine & GCL_TCPRX_SF_WAKE);
+			nrule2 += rx_pop(sf_mine & GCL_TCPRX_SF_RULE2);
+			ndropped += rx_pop(sf_mine & GCL_TCPRX_SF_DROPPED);
+			ntxw += rx_pop(sf_mine & GCL_TCPRX_SF_TXWAKE);
+			nfrtx += rx_pop(sf_mine & GCL_TCPRX_SF_FASTRTX);
+			ndup += rx_pop(sf_mine & GCL_TCPRXF_EV_DUPACK);
+		}
+		if (valid) {
+			k.verdict[j] = (uint8_t)(lane < H ? GCL_TCPRX_FAST : GCL_TCPRX_SLOW);
+			k.sflags[j] = (uint8_t)sf_mine;
+			k.after[j] = after_mine;
+			if (!(of_mine & GCL_OOOF_QUEUED)) { /* a queued entry gets these with its fate */
+				k.copy_len[j] = (uint16_t)copy_mine;
+				k.dst_off[j] = copy_mine ? rel_mine : 0; /* layout adds conn_off[c] */
+				p.oflags[j] = (uint8_t)of_mine;
+				p.skip[j] = (uint16_t)head_mine;
+			}
+		}
+	}
+	/* the queue as it stands: HELD and KEPT, and the entries staged for rxo_qout_kernel */
+	const bool staged = rs < re;
+	const bool mine = lane < qn, held = mine && (e.fl >> 16) != 0;
+	const uint64_t heldmask = __ballot(held);
+	/* a carried entry is staged inside its connection's own input range, a list entry inside its
+	 * connection's own run: disjoint between connections whatever order q_off puts the ranges in */
+	const uint32_t rank_l = (uint32_t)__popcll(heldmask & ((1ull << lane) - 1)), rank_q = lane - rank_l;
+	if (mine) {
+		uint32_t ref = e.idx;
+		if (held) {
+			k.copy_len[e.idx] = 0;
+			k.dst_off[e.idx] = 0;
+			p.oflags[e.idx] = GCL_OOOF_OOO | GCL_OOOF_QUEUED | GCL_OOOF_HELD;
+			p.skip[e.idx] = 0;
+		} else {
+			p.qin_state[e.idx] = GCL_OOOQ_KEPT;
+			ref = p.q[e.idx].z;
+		}
+		if (staged) /* rank_q < qe - qs and rank_l < re - rs: below nq, and below nq + m */
+			p.stage[held ? (size_t)p.nq + rs + rank_l : (size_t)qs + rank_q] = make_uint4(e.seq, e.end, ref, e.fl);
+	}
+	const uint32_t nheld = (uint32_t)__popcll(heldmask);
+	if (lane == 0) {
+		k.out_conn[3 * (size_t)c] = make_uint4(x.l.snd_una, x.l.snd_wnd, x.l.snd_wl1, x.l.snd_wl2);
+		k.out_conn[3 * (size_t)c + 1] = make_uint4(x.l.rcv_nxt, x.l.rcv_wnd, nfast, nslow);
+		k.out_conn[3 * (size_t)c + 2] = make_uint4(nacks, first_slow, (x.l.cnt & 0xFFu) | (x.l.flags & 0xFFu) << 8, 0);
+		p.f.out_ext[c] = make_uint4(nrule2, ndropped, x.fast_rtx_ack, (x.rep_acks & 0xFFu) | (x.xflags & 0xFFu) << 8);
+		p.f.xcnt[c] = make_uint4(ntxw, nfrtx, ndup, nooo);
+		p.ocnt[c] = make_uint4(nqueued, ndrained, nfreed, nhead);
+		p.qmeta[c] = make_uint4(qn | (uint32_t)staged << 8 | (uint32_t)taken << 9, nheld, (uint32_t)heldmask,
+		                        (uint32_t)(heldmask >> 32));
+		k.wakes[c] = wakes;
+	}
+}
+
+/*
+ * One wave per connection, after the scans: lane i writes entry i of the final
+ * queue to qout (from the stage, or straight from q for a connection that had
+ * no segment), and the drained input entries get their connection's offset.
+ */
+__global__ void __launch_bounds__(kRxThreads) rxo_qout_kernel(RxoParams p)
+{
+	const RxParams &k = p.f.k;
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t c = blockIdx.x * kRxWaves + (threadIdx.x >> 6);
+
+	if (c >= k.nconn)
+		return;
+	const uint4 meta = p.qmeta[c];
+	const uint32_t len = (meta.x & 0xFFu) < GCL_TCPOOO_CAP ? meta.x & 0xFFu : GCL_TCPOOO_CAP;
+	const uint64_t heldmask = (uint64_t)meta.w << 32 | meta.z;
+	const bool held = (heldmask >> lane & 1) != 0;
+	const uint32_t rank_l = (uint32_t)__popcll(heldmask & ((1ull << lane) - 1)), rank_q = lane - rank_l;
+	const uint2 rn = k.run[c];
+	const uint64_t re = rn.y < k.m ? rn.y : k.m;
+	const uint64_t rs = rn.x < re ? rn.x : re;
+	uint32_t qs, qe;
+	rxo_range(p, c, &qs, &qe);
+
+	if (lane < len) {
+		const uint64_t at = (uint64_t)p.qout_off[c] + lane;
+		uint4 w = make_uint4(0, 0, 0, 0);
+		if (meta.x >> 8 & 1) { /* staged: the bounds hold again whatever the workspace holds */
+			if (held ? rs + rank_l < re : qs + rank_q < qe)
+				w = p.stage[held ? (size_t)p.nq + rs + rank_l : (size_t)qs + rank_q];
+		} else if (qs + lane < qe) {
+			w = p.q[qs + lane];
+			w.w &= 0xFFFFu;
+		}
+		if (at < p.q_out_cap)
+			p.qout[at] = w;
+	}
+	if ((meta.x >> 9 & 1) && lane < qe - qs) {
+		const uint32_t i = qs + lane;
+		if (p.qin_state[i] == GCL_OOOQ_DRAINED && p.qin_len[i])
+			p.qin_dst_off[i] += k.conn_off[c];
+	}
+}
+
+/* the sixteen counters of the call that the walk decides, summed over the connections */
+__global__ void __launch_bounds__(kRxThreads) rxo_counts_kernel(RxoParams p)
+{
+	constexpr int N = 16;
+	const RxParams &k = p.f.k;
+	__shared__ unsigned long long blk[N];
+	unsigned long long v[N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+	if (threadIdx.x < N)
+		blk[threadIdx.x] = 0;
+	__syncthreads();
+	for (uint32_t c = blockIdx.x * kRxThreads + threadIdx.x; c < k.nconn; c += gridDim.x * kRxThreads) {
+		const uint4 o1 = k.out_conn[3 * (size_t)c + 1], o2 = k.out_conn[3 * (size_t)c + 2];
+		const uint4 ex = p.f.out_ext[c], xc = p.f.xcnt[c], oc = p.ocnt[c];
+		v[0] += o1.z;
+		v[1] += o1.w;
+		v[2] += (uint32_t)(o1.x - k.conn[3 * (size_t)c + 1].y);
+		v[3] += o2.x;
+		v[4] += k.wakes[c];
+		v[5] += ex.x;
+		v[6] += xc.x;
+		v[7] += xc.y;
+		v[8] += xc.z;
+		v[9] += ex.y;
+		v[10] += xc.w;
+		v[11] += oc.x;
+		v[12] += oc.y;
+		v[13] += oc.z;
+		v[14] += oc.w;
+		v[15] += p.qmeta[c].y;
+	}
+#pragma unroll
+	for (int x = 0; x < N; x++) {
+		for (int d = 32; d; d >>= 1) {
+			const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v[x], d);
+			const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v[x] >> 32), d);
+			v[x] += (unsigned long long)hi << 32 | lo;
+		}
+		if ((threadIdx.x & 63) == 0 && v[x])
+			atomicAdd(&blk[x], v[x]);
+	}
+	__syncthreads();
+	if (threadIdx.x < N && blk[threadIdx.x]) {
+		const uint32_t slot[N] = {GCL_TCPRXC_FAST, GCL_TCPRXC_SLOW, GCL_TCPRXC_BYTES, GCL_TCPRXC_ACKS,
+		                          GCL_TCPRXC_WAKES, GCL_TCPRXFC_RULE2, GCL_TCPRXFC_TXWAKES, GCL_TCPRXFC_FASTRTX,
+		                          GCL_TCPRXFC_DUPACKS, GCL_TCPRXFC_DROPPED, GCL_TCPRXOC_OOO, GCL_TCPRXOC_QUEUED,
+		                          GCL_TCPRXOC_DRAINED, GCL_TCPRXOC_FREED, GCL_TCPRXOC_HEADCLIP, GCL_TCPRXOC_HELD};
+		atomicAdd(k.counts + slot[threadIdx.x], blk[threadIdx.x]);
+	}
+}
+
 /* ---- the workspace ---- */
 
 struct RxGeom {
@@ -840,9 +1257,21 @@ struct RxFull {
 	struct gcl_tcp_conn_ext *out_ext;
 };
 
+/* what gcl_tcp_rx_ooo adds to a gcl_tcp_rx_full call; NULL: not that call */
+struct RxOoo {
+	const struct gcl_tcprxo_in *in;
+	const struct gcl_tcprxo_out *out;
+};
+
+/* the bytes gcl_tcp_rx_ooo keeps behind gcl_tcp_rx_full's workspace: ocnt, qmeta, qsum, stage */
+static size_t rxo_extra(uint64_t m, uint32_t nconn, uint32_t nq)
+{
+	return 32 * (size_t)nconn + rx_up16(4 * (((size_t)nconn + kRxChunk - 1) / kRxChunk)) + 16 * ((size_t)nq + m);
+}
+
 static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprx_in *in,
-                  const struct gcl_tcprx_out *out, const RxFull *full, uint64_t *counts, void *workspace,
-                  size_t workspace_bytes, void *hip_stream)
+                  const struct gcl_tcprx_out *out, const RxFull *full, const RxOoo *ooo, uint64_t *counts,
+                  void *workspace, size_t workspace_bytes, void *hip_stream)
 {
 	hipStream_t s = (hipStream_t)hip_stream;
 	RxGeom g;
@@ -862,8 +1291,21 @@ static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl
 	    rx_misaligned(out->dst_off, 8) || rx_misaligned(out->out_conn, 16) ||
 	    rx_misaligned(out->conn_off, 8) || rx_misaligned(counts, 8))
 		return -EINVAL;
-	/* gcl_tcp_rx_full keeps xcnt behind gcl_tcp_rx's workspace */
-	const size_t xbytes = full ? 16 * (size_t)in->nconn : 0;
+	if (ooo) {
+		const struct gcl_tcprxo_in *oi = ooo->in;
+		const struct gcl_tcprxo_out *oo = ooo->out;
+
+		if (!oo || oi->nq > (1u << 31) || !oo->qout_off || !oo->totals || (in->m && (!oo->oflags || !oo->skip)) ||
+		    (oi->nq && (!oi->q || !oo->qin_state || !oo->qin_skip || !oo->qin_len || !oo->qin_dst_off)) ||
+		    (oi->q_out_cap && !oo->qout))
+			return -EINVAL;
+		if (rx_misaligned(oi->q_off, 4) || rx_misaligned(oi->q, 16) || rx_misaligned(oo->skip, 2) ||
+		    rx_misaligned(oo->qin_skip, 2) || rx_misaligned(oo->qin_len, 2) || rx_misaligned(oo->qin_dst_off, 8) ||
+		    rx_misaligned(oo->qout_off, 4) || rx_misaligned(oo->qout, 16) || rx_misaligned(oo->totals, 8))
+			return -EINVAL;
+	}
+	/* gcl_tcp_rx_full keeps xcnt behind gcl_tcp_rx's workspace, gcl_tcp_rx_ooo its own behind that */
+	const size_t xbytes = (full ? 16 * (size_t)in->nconn : 0) + (ooo ? rxo_extra(in->m, in->nconn, ooo->in->nq) : 0);
 	if (!workspace || rx_misaligned(workspace, 16) || workspace_bytes < g.bytes + xbytes)
 		return -EINVAL;
 	if (in->m && (!b->frames || b->frames_len == UINT64_MAX || b->n > (1ull << 40) ||
@@ -918,6 +1360,21 @@ static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl
 	if (k.range_len == 0)
 		k.range_len = 64;
 
+	if (ooo) { /* what no walk may reach: entries that are NA, NOCONN or DROP, queue entries of no taken connection */
+		const struct gcl_tcprxo_out *oo = ooo->out;
+		const size_t nq = ooo->in->nq;
+
+		if ((in->m && (hipMemsetAsync(oo->oflags, 0, in->m, s) != hipSuccess ||
+		               hipMemsetAsync(oo->skip, 0, 2 * (size_t)in->m, s) != hipSuccess)) ||
+		    (nq && (hipMemsetAsync(oo->qin_state, GCL_OOOQ_UNTOUCHED, nq, s) != hipSuccess ||
+		            hipMemsetAsync(oo->qin_skip, 0, 2 * nq, s) != hipSuccess ||
+		            hipMemsetAsync(oo->qin_len, 0, 2 * nq, s) != hipSuccess ||
+		            hipMemsetAsync(oo->qin_dst_off, 0, 8 * nq, s) != hipSuccess)))
+			return -EIO;
+		if (in->nconn == 0 && (hipMemsetAsync(oo->qout_off, 0, 4, s) != hipSuccess ||
+		                       hipMemsetAsync(oo->totals, 0, 8, s) != hipSuccess))
+			return -EIO;
+	}
 	if (in->nconn == 0) { /* every TCP segment is NOCONN: nothing to group, walk or lay out */
 		if (in->m)
 			hipLaunchKernelGGL(rx_parse_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
@@ -946,10 +1403,47 @@ static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl
 		hipLaunchKernelGGL(rx_runs_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k, sorted);
 	}
 	RxfParams kf = {k, nullptr, nullptr, nullptr};
+	RxoParams ko = {};
+	const dim3 wgrid((in->nconn + kRxWaves - 1) / kRxWaves);
 	if (full) {
 		kf.rep_acks = full->rep_acks;
 		kf.out_ext = (uint4 *)full->out_ext;
 		kf.xcnt = (uint4 *)(ws + g.bytes);
+	}
+	if (ooo) {
+		const struct gcl_tcprxo_in *oi = ooo->in;
+		const struct gcl_tcprxo_out *oo = ooo->out;
+		uint8_t *at = ws + g.bytes + 16 * (size_t)in->nconn;
+
+		ko.f = kf;
+		ko.q_off = oi->q_off;
+		ko.q = (const uint4 *)oi->q;
+		ko.nq = oi->nq;
+		ko.q_out_cap = oi->q_out_cap;
+		ko.oflags = oo->oflags;
+		ko.skip = oo->skip;
+		ko.qin_state = oo->qin_state;
+		ko.qin_skip = oo->qin_skip;
+		ko.qin_len = oo->qin_len;
+		ko.qin_dst_off = (unsigned long long *)oo->qin_dst_off;
+		ko.qout_off = oo->qout_off;
+		ko.qout = (uint4 *)oo->qout;
+		ko.totals = (unsigned long long *)oo->totals;
+		ko.ocnt = (uint4 *)at;
+		at += 16 * (size_t)in->nconn;
+		ko.qmeta = (uint4 *)at;
+		at += 16 * (size_t)in->nconn;
+		ko.qsum = (uint32_t *)at;
+		at += rx_up16(4 * (((size_t)in->nconn + kRxChunk - 1) / kRxChunk));
+		ko.stage = (uint4 *)at;
+		hipLaunchKernelGGL(rxo_walk_kernel, wgrid, dim3(kRxThreads), 0, s, ko, sorted);
+		const RxQoutIo io = {ko.qmeta, ko.qout_off, ko.totals, in->nconn};
+		const uint32_t nchunks = (in->nconn + kRxChunk - 1) / kRxChunk;
+		hipLaunchKernelGGL(rx_scan_sum_kernel<RxQoutIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn, ko.qsum);
+		hipLaunchKernelGGL(rx_scan_top_kernel<RxQoutIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, ko.qsum, nchunks);
+		hipLaunchKernelGGL(rx_scan_apply_kernel<RxQoutIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn,
+		                   ko.qsum);
+	} else if (full) {
 		hipLaunchKernelGGL(rxf_walk_kernel, dim3((in->nconn + kRxWaves - 1) / kRxWaves), dim3(kRxThreads), 0, s,
 		                   kf, sorted);
 	} else {
@@ -965,7 +1459,13 @@ static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl
 		                   k.lsum);
 	}
 	const dim3 cgrid(std::min<uint32_t>((in->nconn + kRxThreads - 1) / kRxThreads, cus * 2));
-	if (full) {
+	if (ooo) {
+		if (in->m)
+			hipLaunchKernelGGL(rxf_fix_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
+		hipLaunchKernelGGL(rxo_qout_kernel, wgrid, dim3(kRxThreads), 0, s, ko);
+		if (counts)
+			hipLaunchKernelGGL(rxo_counts_kernel, cgrid, dim3(kRxThreads), 0, s, ko);
+	} else if (full) {
 		if (in->m)
 			hipLaunchKernelGGL(rxf_fix_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
 		if (counts)
@@ -983,7 +1483,7 @@ extern "C" int gcl_tcp_rx(struct gcl_ctx *c, const struct gcl_batch *b, const st
                           const struct gcl_tcprx_out *out, uint64_t *counts, void *workspace,
                           size_t workspace_bytes, void *hip_stream)
 {
-	return rx_run(c, b, in, out, nullptr, counts, workspace, workspace_bytes, hip_stream);
+	return rx_run(c, b, in, out, nullptr, nullptr, counts, workspace, workspace_bytes, hip_stream);
 }
 
 extern "C" int gcl_tcp_rx_full_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, size_t *bytes)
@@ -1006,5 +1506,30 @@ extern "C" int gcl_tcp_rx_full(struct gcl_ctx *c, const struct gcl_batch *b, con
 	                                 in->conn, in->nconn, in->blocks};
 	const RxFull full = {in->rep_acks, out_ext};
 
-	return rx_run(c, b, &rin, out, &full, counts, workspace, workspace_bytes, hip_stream);
+	return rx_run(c, b, &rin, out, &full, nullptr, counts, workspace, workspace_bytes, hip_stream);
+}
+
+extern "C" int gcl_tcp_rx_ooo_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, uint32_t nq, size_t *bytes)
+{
+	RxGeom g;
+
+	if (!bytes || nq > (1u << 31) || rx_geometry(m, nconn, blocks, &g))
+		return -EINVAL;
+	*bytes = g.bytes + 16 * (size_t)nconn + rxo_extra(m, nconn, nq);
+	return 0;
+}
+
+extern "C" int gcl_tcp_rx_ooo(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprxo_in *in,
+                              const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext,
+                              const struct gcl_tcprxo_out *ooo, uint64_t *counts, void *workspace,
+                              size_t workspace_bytes, void *hip_stream)
+{
+	if (!in || in->size != sizeof(*in))
+		return -EINVAL;
+	const struct gcl_tcprx_in rin = {sizeof(rin), in->align, in->order, in->m, in->sock, in->l4_status,
+	                                 in->conn, in->nconn, in->blocks};
+	const RxFull full = {in->rep_acks, out_ext};
+	const RxOoo o = {in, ooo};
+
+	return rx_run(c, b, &rin, out, &full, &o, counts, workspace, workspace_bytes, hip_stream);
 }

@@ -126,6 +126,14 @@ TCPX_TXWAKE, TCPX_FASTRTX = 0x01, 0x02
 TCPRXFC_RULE2, TCPRXFC_TXWAKES, TCPRXFC_FASTRTX, TCPRXFC_DUPACKS, TCPRXFC_DROPPED, TCPRXFC_NR = 8, 9, 10, 11, 12, 13
 TCP_CONN_EXT_DTYPE = np.dtype([("nrule2", "<u4"), ("ndropped", "<u4"), ("fast_rtx_ack", "<u4"),
                                ("rep_acks", "u1"), ("xflags", "u1"), ("pad", "u1", (2,))])
+# gcl_tcp_rx_ooo: the queue cap, the flag bits it adds, oflags, qin_state, the counters behind
+# gcl_tcp_rx_full's thirteen and struct gcl_tcp_ooo_ent
+TCPOOO_CAP, TCPC_ESTABLISHED, TCPX_QSKIP = 64, 0x80, 0x04
+OOOF_OOO, OOOF_QUEUED, OOOF_HEADCLIP, OOOF_LATE_DRAINED, OOOF_LATE_FREED, OOOF_HELD = 1, 2, 4, 8, 0x10, 0x20
+OOOQ_UNTOUCHED, OOOQ_KEPT, OOOQ_FREED, OOOQ_DRAINED = 0, 1, 2, 3
+(TCPRXOC_OOO, TCPRXOC_QUEUED, TCPRXOC_DRAINED, TCPRXOC_FREED, TCPRXOC_HEADCLIP, TCPRXOC_HELD,
+ TCPRXOC_NR) = 13, 14, 15, 16, 17, 18, 19
+TCP_OOO_ENT_DTYPE = np.dtype([("seq", "<u4"), ("end", "<u4"), ("ref", "<u4"), ("flags", "<u2"), ("src", "<u2")])
 # gcl_tcp_tick / gcl_tcp_rx_acks: the timer flags, the action bits (bits 0..6 are also the first
 # counter slots), the segment kinds, the counters, the caps, the TCP states the sweep tests,
 # struct gcl_tcp_tmr, struct gcl_tcp_tmr_out and struct gcl_tcp_addr
@@ -413,6 +421,21 @@ class GclTcprxfIn(ctypes.Structure):
     _fields_ = GclTcprxIn._fields_ + [("rep_acks", ctypes.c_void_p)]
 
 
+class GclTcprxoIn(ctypes.Structure):
+    _fields_ = GclTcprxfIn._fields_ + [("q_off", ctypes.c_void_p), ("q", ctypes.c_void_p),
+                                       ("nq", ctypes.c_uint32), ("q_out_cap", ctypes.c_uint32)]
+
+
+# struct gcl_tcprxo_out: (field, bytes per element, which count it is sized by)
+TCPRXO_OUT_FIELDS = (("oflags", 1, "m"), ("skip", 2, "m"), ("qin_state", 1, "nq"), ("qin_skip", 2, "nq"),
+                     ("qin_len", 2, "nq"), ("qin_dst_off", 8, "nq"), ("qout_off", 4, "nconn1"),
+                     ("qout", 16, "cap"), ("totals", 8, "one"))
+
+
+class GclTcprxoOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f, _, _ in TCPRXO_OUT_FIELDS]
+
+
 TCPRX_ENTRY_FIELDS = ("verdict", "sflags", "rcv_nxt_after", "copy_len", "dst_off")
 TCPRX_OUT_FIELDS = TCPRX_ENTRY_FIELDS + ("out_conn", "conn_off")
 
@@ -472,6 +495,7 @@ assert ctypes.sizeof(GclCtlsegOut) == 48 and TCP_TMR_DTYPE.itemsize == 64 and TC
 assert TCP_ADDR_DTYPE.itemsize == 16
 assert ctypes.sizeof(GclTcprxIn) == 56 and ctypes.sizeof(GclTcprxOut) == 56
 assert ctypes.sizeof(GclTcprxfIn) == 64 and TCP_CONN_EXT_DTYPE.itemsize == 16
+assert ctypes.sizeof(GclTcprxoIn) == 88 and ctypes.sizeof(GclTcprxoOut) == 72 and TCP_OOO_ENT_DTYPE.itemsize == 16
 assert TCP_CONN_DTYPE.itemsize == 48 and TCP_CONN_OUT_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclSegIn) == 64 and ctypes.sizeof(GclSegOut) == 104 and SEG_SEND_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclTxhIn) == 88 and ctypes.sizeof(GclTxhNet) == 20 and TXH_DESC_DTYPE.itemsize == 32
@@ -583,6 +607,12 @@ def _load():
                                   ctypes.POINTER(GclTcprxOut), vp, vp, vp, ctypes.c_size_t, vp]),
         "gcl_tcp_rx_full_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxfIn),
                                        ctypes.POINTER(GclTcprxOut), vp, vp]),
+        "gcl_tcp_rx_ooo_workspace": (i32, [u64, u32, u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_rx_ooo": (i32, [vp, ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxoIn),
+                                 ctypes.POINTER(GclTcprxOut), vp, ctypes.POINTER(GclTcprxoOut), vp, vp,
+                                 ctypes.c_size_t, vp]),
+        "gcl_tcp_rx_ooo_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxoIn),
+                                      ctypes.POINTER(GclTcprxOut), vp, ctypes.POINTER(GclTcprxoOut), vp]),
         "gcl_tcp_tick_workspace": (i32, [u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
         "gcl_tcp_tick": (i32, [vp, ctypes.POINTER(GclTickIn), ctypes.POINTER(GclTickOut), vp, vp,
                                ctypes.c_size_t, vp]),
@@ -1186,6 +1216,71 @@ def tcp_rx_full_workspace(m, nconn, blocks=0):
     """gcl_tcp_rx_full_workspace: bytes of device scratch a call over @m entries and @nconn connections takes."""
     need = ctypes.c_size_t()
     _check(lib.gcl_tcp_rx_full_workspace(m, nconn, blocks, ctypes.byref(need)), "gcl_tcp_rx_full_workspace")
+    return need.value
+
+
+def _tcprxo_sizes(m, nconn, nq, q_out_cap):
+    return {"m": m, "nq": nq, "nconn1": nconn + 1, "cap": q_out_cap, "one": 1}
+
+
+def _tcprxo_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status, conn, nconn,
+                    align, blocks, out, counts, rep_acks, q_off, q, nq, q_out_cap):
+    """The four structs of gcl_tcp_rx_ooo / gcl_tcp_rx_ooo_host, sizes checked;
+    @out maps TCPRX_OUT_FIELDS, "out_ext" and TCPRXO_OUT_FIELDS to buffers."""
+    if counts is not None and _nbytes(counts) < 8 * TCPRXOC_NR:
+        raise ValueError("counts buffer too small")
+    if q_off is not None and _nbytes(q_off) < 4 * (nconn + 1):
+        raise ValueError("q_off too small")
+    if q is not None and _nbytes(q) < 16 * nq:
+        raise ValueError("q too small")
+    size = _tcprxo_sizes(m, nconn, nq, q_out_cap)
+    for f, w, by in TCPRXO_OUT_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < w * size[by]:
+            raise ValueError(f"{f} too small")
+    b, fin, rout = _tcprxf_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status,
+                                   conn, nconn, align, blocks, out, None, rep_acks)
+    oin = GclTcprxoIn(size=ctypes.sizeof(GclTcprxoIn), align=align, order=fin.order, m=m, sock=fin.sock,
+                      l4_status=fin.l4_status, conn=fin.conn, nconn=nconn, blocks=blocks, rep_acks=fin.rep_acks,
+                      q_off=_ptr(q_off), q=_ptr(q), nq=nq, q_out_cap=q_out_cap)
+    oout = GclTcprxoOut(**{f: _ptr(out[f]) for f, _, _ in TCPRXO_OUT_FIELDS})
+    return b, oin, rout, oout
+
+
+def tcp_rx_ooo_host(frames, pkt_len, sock, conn, stride=0, offs=None, n=None, frames_len=None, order=None,
+                    m=None, l4_status=None, nconn=None, align=0, blocks=0, rep_acks=None, q_off=None, q=None,
+                    nq=None, q_out_cap=0, out=None, counts=None):
+    """gcl_tcp_rx_ooo_host: the rule of Classifier.tcp_rx_ooo on the CPU over
+    numpy arrays: tcp_rx_full_host's arguments, the input queues (@q_off
+    u32[nconn + 1] or None, @q TCP_OOO_ENT_DTYPE[nq]) and @q_out_cap; in @out
+    also the fields of TCPRXO_OUT_FIELDS.  @counts is a u64[TCPRXOC_NR],
+    accumulated.  Returns the dict."""
+    n = len(pkt_len) if n is None else n
+    m = _pay_m(n, m, order)
+    nconn = len(conn) if nconn is None else nconn
+    nq = (0 if q is None else len(q)) if nq is None else nq
+    out = dict(out or {})
+    size = _tcprxo_sizes(m, nconn, nq, q_out_cap)
+    for f, dt, k in (("verdict", np.uint8, m), ("sflags", np.uint8, m), ("rcv_nxt_after", np.uint32, m),
+                     ("copy_len", np.uint16, m), ("dst_off", np.uint64, m),
+                     ("out_conn", TCP_CONN_OUT_DTYPE, nconn), ("conn_off", np.uint64, nconn + 1),
+                     ("out_ext", TCP_CONN_EXT_DTYPE, nconn)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    for f, w, by in TCPRXO_OUT_FIELDS:
+        if f not in out:
+            out[f] = np.zeros(max(size[by], 1), dtype=TCP_OOO_ENT_DTYPE if f == "qout" else f"<u{w}")
+    b, oin, rout, oout = _tcprxo_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status,
+                                         conn, nconn, align, blocks, out, counts, rep_acks, q_off, q, nq,
+                                         q_out_cap)
+    _check(lib.gcl_tcp_rx_ooo_host(ctypes.byref(b), ctypes.byref(oin), ctypes.byref(rout), _ptr(out["out_ext"]),
+                                   ctypes.byref(oout), _ptr(counts)), "gcl_tcp_rx_ooo_host")
+    return out
+
+
+def tcp_rx_ooo_workspace(m, nconn, blocks=0, nq=0):
+    """gcl_tcp_rx_ooo_workspace: bytes of device scratch a call over @m entries, @nconn connections and @nq input queue entries takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_rx_ooo_workspace(m, nconn, blocks, nq, ctypes.byref(need)), "gcl_tcp_rx_ooo_workspace")
     return need.value
 
 
@@ -1974,6 +2069,48 @@ class Classifier:
         _check(lib.gcl_tcp_rx_full(self._ctx, ctypes.byref(b), ctypes.byref(fin), ctypes.byref(rout),
                                    _ptr(out["out_ext"]), _ptr(counts), _ptr(ws), _nbytes(ws), stream),
                "gcl_tcp_rx_full")
+        return out
+
+    def tcp_rx_ooo(self, frames, n, pkt_len, sock, conn, nconn, stride=0, offs=None, frames_len=None,
+                   order=None, m=None, l4_status=None, align=0, blocks=0, rep_acks=None, q_off=None, q=None,
+                   nq=0, q_out_cap=0, out=None, counts=None, workspace=None, stream=None):
+        """gcl_tcp_rx_ooo: tcp_rx_conn with its established slow path and the
+        out-of-order queue for one runtime's list on the GPU, asynchronous.
+        The arguments are tcp_rx_full's; @q_off is a device int32[nconn + 1]
+        (None: every queue is empty), @q a device uint8[nq, 16] of
+        TCP_OOO_ENT_DTYPE records, @q_out_cap the entries out["qout"] holds.
+        @out also holds the fields of TCPRXO_OUT_FIELDS and @counts is a device
+        u64[TCPRXOC_NR], accumulated.  Returns the dict: copy_batch takes
+        src_off + skip, copy_len and dst_off; qout_off and qout are the queues
+        to relink, totals[0] the entries wanted."""
+        import torch
+        m = _pay_m(n, m, order)
+        dev = frames.device if hasattr(frames, "device") else None
+        out = dict(out or {})
+        mm = max(m, 1)
+        size = _tcprxo_sizes(m, nconn, nq, q_out_cap)
+        for f, dt, shape in (("verdict", torch.uint8, (mm,)), ("sflags", torch.uint8, (mm,)),
+                             ("rcv_nxt_after", torch.int32, (mm,)), ("copy_len", torch.int16, (mm,)),
+                             ("dst_off", torch.int64, (mm,)), ("out_conn", torch.uint8, (max(nconn, 1), 48)),
+                             ("conn_off", torch.int64, (nconn + 1,)),
+                             ("out_ext", torch.uint8, (max(nconn, 1), 16))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        for f, w, by in TCPRXO_OUT_FIELDS:
+            if f not in out:
+                out[f] = torch.empty((max(size[by], 1), w), dtype=torch.uint8, device=dev)
+        b, oin, rout, oout = _tcprxo_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock,
+                                             l4_status, conn, nconn, align, blocks, out, counts, rep_acks, q_off,
+                                             q, nq, q_out_cap)
+        ws = workspace
+        if ws is None:
+            need = tcp_rx_ooo_workspace(m, nconn, blocks, nq)
+            ws = getattr(self, "_tcprx_ws", None)
+            if ws is None or ws.numel() < need or ws.device != out["conn_off"].device:
+                ws = self._tcprx_ws = torch.empty(need, dtype=torch.uint8, device=out["conn_off"].device)
+        _check(lib.gcl_tcp_rx_ooo(self._ctx, ctypes.byref(b), ctypes.byref(oin), ctypes.byref(rout),
+                                  _ptr(out["out_ext"]), ctypes.byref(oout), _ptr(counts), _ptr(ws), _nbytes(ws),
+                                  stream), "gcl_tcp_rx_ooo")
         return out
 
     def _ctlseg_device_arrays(self, out, seg_cap, dev):

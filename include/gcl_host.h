@@ -260,6 +260,21 @@ int gcl_tcp_rx_full_host(const struct gcl_batch *b, const struct gcl_tcprxf_in *
                          const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext, uint64_t *counts);
 
 /*
+ * gcl_tcp_rx_ooo_host - the rule of gcl_tcp_rx_ooo (gclassify.h) on the CPU
+ * over host pointers: the list is threaded per connection, then every
+ * connection walks its segments in list order with its out-of-order queue in a
+ * local array, composed of the pieces of csrc/gcl_tcprxo.h that the kernel
+ * composes.  It allocates 4 (m + 2 nconn) bytes for the threading and frees
+ * them before it returns; no workspace.  @counts is a host
+ * u64[GCL_TCPRXOC_NR], ACCUMULATED, may be NULL.  The same outputs byte for
+ * byte, the same counts and the same guarantee.  0, -EINVAL for what
+ * gcl_tcp_rx_ooo refuses (the ctx and the workspace apart), or -ENOMEM.
+ */
+int gcl_tcp_rx_ooo_host(const struct gcl_batch *b, const struct gcl_tcprxo_in *in,
+                        const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext,
+                        const struct gcl_tcprxo_out *ooo, uint64_t *counts);
+
+/*
  * gcl_tcp_tick_host, gcl_tcp_rx_acks_host - the rules of gcl_tcp_tick and
  * gcl_tcp_rx_acks (gclassify.h) on the CPU over host pointers, for the sweeps
  * and lists the GPU did not see: tcp_worker's walk with tcp_handle_timeouts and

@@ -1950,6 +1950,172 @@ int gcl_tcp_rx_full(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct
                     void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /*
+ * TCP receive with the out-of-order queue: gcl_tcp_rx_ooo stands where
+ * gcl_tcp_rx_full stands, takes the same inputs and behaves exactly as it
+ * does, except that out-of-order and head-clipped text is handled instead of
+ * stopping the connection: tcp_rx_text and tcp_rx_append_text
+ * (runtime/net/tcp_in.c:64-169) with c->rxq_ooo.  Every connection brings its
+ * queue in and gets it back as it stands after the list.  This closes the
+ * established-state data path of tcp_in.c.
+ *
+ *   gcl_l4_payload -> gcl_tcp_rx_ooo -> gcl_copy_batch (src_off + skip)
+ *                  -> gcl_tcp_rx_acks (the duplicate ACKs of :574 among them)
+ *                  -> gcl_tcp_txq
+ *
+ * The queue of a connection is an ordered array of at most GCL_TCPOOO_CAP
+ * entries {seq, end, ref, flags, src}, the head first.  Connection c's input
+ * queue is q[min(q_off[c], nq), min(q_off[c + 1], nq)), empty when that range
+ * is reversed; q_off == NULL means every queue is empty.  The input queue
+ * itself, not GCL_TCPC_ELIGIBLE, says whether the queue is empty.  No order is
+ * assumed on it: the result is what the reference's walk gives on that list.
+ * A connection is TAKEN when its flags have GCL_TCPC_ELIGIBLE or
+ * GCL_TCPC_ESTABLISHED (state == ESTABLISHED whatever the queue holds; never
+ * set in out_conn.flags), its input queue has at most GCL_TCPOOO_CAP entries
+ * and none of them carries FIN (flags & 0x01: a drained FIN would change state
+ * in mid-segment).  The queue of a connection whose flags have neither bit is
+ * not looked at, nor are more than GCL_TCPOOO_CAP entries.  A connection that
+ * is not taken stops at its first segment as in gcl_tcp_rx_full, gets an empty
+ * output queue and GCL_OOOQ_UNTOUCHED on its input entries, and, when its
+ * input range was not empty, GCL_TCPX_QSKIP in xflags: the runtime still holds
+ * that queue (this departs from marking every connection that is not taken:
+ * one without a queue gets gcl_tcp_rx_full's out_ext byte for byte).  The
+ * ranges of two connections must not overlap; they may follow each other in
+ * any order (q_off need not be non-decreasing).  Where they do overlap, the
+ * outputs of those connections and of the shared entries are unspecified, and
+ * still in bounds.
+ *
+ * For one segment of connection c, in list order, after the lines NA, NOCONN
+ * and DROP of gcl_tcp_rx:
+ *  1. The fast path, exactly when gcl_tcp_rx's rule says FAST and the LIVE
+ *     queue is empty (:233): the queue as it stands now, so a connection whose
+ *     queue drains empty in mid-list goes back to the fast path.
+ *  2. The segment STOPS the connection (verdict SLOW, state and queue frozen as
+ *     before the segment) when the connection has stopped already, is not
+ *     taken, the segment carries FIN, RST, URG or SYN, or it would be inserted
+ *     (:124-135) while the live queue holds GCL_TCPOOO_CAP entries.  The
+ *     reference's own bound, TCP_OOO_MAX_SIZE = 2048, cannot be reached below
+ *     this cap; the cap stops the connection, it does not drop the segment.
+ *  3. Every other segment runs gcl_tcp_rx_full's step 3 unchanged up to the
+ *     text; for len > 0 the text step is tcp_rx_text:
+ *     wraps_lte(seq, rcv_nxt), the in-order branch: wake on PSH or
+ *       GCL_TCPC_RXQ; the head is clipped by rcv_nxt - seq bytes, then the tail
+ *       to the window; rcv_nxt and rcv_wnd move.
+ *     else the out-of-order branch: walk the queue from its tail; the first
+ *       entry e with wraps_gt(end, e.end): insert after it; an entry with
+ *       wraps_gte(seq, e.seq) before that: the segment is refused (DROPPED),
+ *       no drain runs and the delayed-ACK lines below still run; no such
+ *       entry: insert at the head.
+ *     the drain (:140-163), from the head: free every entry with
+ *       wraps_lte(e.end, rcv_nxt); stop at wraps_gt(e.seq, rcv_nxt); else pop
+ *       the entry, wake, and append it with both clips, also when the window
+ *       has reached 0 and clips it to zero bytes.
+ *     then: wake when rcv_wnd == 0; ++acks_delayed_cnt >= 2: do_ack, else arm
+ *       the delayed ACK; do_ack also when the queue is not empty (:574).
+ *     WAKE, ACK_NOW and rcv_nxt_after belong to the segment being processed,
+ *     its drain included.
+ *
+ * Outputs.  @out and @out_ext are gcl_tcp_rx_full's.  All accepted bytes of a
+ * connection still form [conn[c].rcv_nxt, out_conn[c].rcv_nxt), so fast_bytes,
+ * conn_off and the layout are gcl_tcp_rx's; copy_len is the accepted byte
+ * count after both clips and dst_off = conn_off[c] + (clipped seq -
+ * conn[c].rcv_nxt) where copy_len > 0.  @ooo adds, per list entry, oflags[j]
+ * (GCL_OOOF_*) and skip[j], the head bytes to add to gcl_l4_payload's src_off;
+ * gcl_copy_batch with src_off + skip, copy_len and dst_off leaves the stream
+ * contiguous and in sequence order.  An entry queued in this call and drained
+ * later in it gets its copy_len, skip and dst_off then (LATE_DRAINED), one
+ * freed as already received LATE_FREED, one still queued at the end HELD with
+ * copy_len = 0: the runtime keeps the frame.  Per input queue entry i < nq:
+ * qin_state[i] (GCL_OOOQ_*), and for a DRAINED one qin_skip[i], qin_len[i]
+ * (each saturates at 65535, more than any frame holds) and qin_dst_off[i], its
+ * place in the same layout; else 0.  The output queues: qout_off[c], c <=
+ * nconn, is the whole prefix sum of the final queue lengths, and entry k of
+ * connection c's queue is qout[qout_off[c] + k]: seq, end, flags as they
+ * stand (unclipped), src 0 with the input's ref for one carried over from the
+ * input, src 1 with ref = j for list entry j of this call.  Entries at and
+ * past q_out_cap are not written; totals[0] = qout_off[nconn], the entries
+ * wanted (what q_out_cap should have been).
+ *
+ * @counts is a device u64[GCL_TCPRXOC_NR], ACCUMULATED, may be NULL: the
+ * thirteen of gcl_tcp_rx_full (BYTES: every accepted byte, the drained input
+ * entries' among them), then OOO (segments that took the out-of-order branch),
+ * QUEUED (inserted), DRAINED and FREED (entries, of either source), HEADCLIP
+ * (appends that lost head bytes) and HELD.
+ *
+ * Guarantee: gcl_tcp_rx_full's, and no content of q_off or q causes an access
+ * outside q_off[0, nconn], q[0, nq), the outputs (@ooo's per-entry arrays m
+ * elements, its per-queue-entry arrays nq, qout_off[0, nconn], qout[0,
+ * q_out_cap), totals[0]) and the workspace.
+ *
+ * What stays with the runtime: FIN / RST / URG / SYN and every other state,
+ * which need the connection object itself; the mbufs (ref is the handle:
+ * free the FREED, DROPPED and LATE_FREED ones, keep the HELD ones, relink
+ * rxq_ooo from qout); the wake-ups, the ACKs, the timers and the lock, as for
+ * gcl_tcp_rx_full.
+ *
+ * gcl_tcp_rx_ooo_workspace, gcl_tcp_rx_ooo - as gcl_tcp_rx_full's, the
+ *   workspace also sized by nq: asynchronous, launches ordered by the stream
+ *   alone, no block waits for another, no atomic's order decides a result, no
+ *   allocation, no host synchronisation.  -EINVAL for what gcl_tcp_rx_full
+ *   refuses; nq > 2^31; a NULL ooo, qout_off or totals; with m > 0 a NULL
+ *   oflags or skip; with nq > 0 a NULL q, qin_state, qin_skip, qin_len or
+ *   qin_dst_off; with q_out_cap > 0 a NULL qout; any of them not aligned to
+ *   its element (q, qout: 16 B).
+ */
+#define GCL_TCPOOO_CAP 64            /* queue entries per connection: one per lane of a wave */
+#define GCL_TCPC_ESTABLISHED 0x80    /* gcl_tcp_conn.flags: state == ESTABLISHED, whatever rxq_ooo holds */
+#define GCL_TCPX_QSKIP 0x04          /* gcl_tcp_conn_ext.xflags: the input queue was not taken */
+/* oflags[j] */
+#define GCL_OOOF_OOO          0x01   /* took tcp_rx_text's out-of-order branch */
+#define GCL_OOOF_QUEUED       0x02   /* was inserted into the queue */
+#define GCL_OOOF_HEADCLIP     0x04   /* skip[j] > 0 */
+#define GCL_OOOF_LATE_DRAINED 0x08   /* queued here, appended by a later drain of this call */
+#define GCL_OOOF_LATE_FREED   0x10   /* queued here, freed as already received */
+#define GCL_OOOF_HELD         0x20   /* queued here and still queued: in qout */
+/* qin_state[i] */
+#define GCL_OOOQ_UNTOUCHED 0         /* of no taken connection */
+#define GCL_OOOQ_KEPT      1         /* still queued: in qout */
+#define GCL_OOOQ_FREED     2
+#define GCL_OOOQ_DRAINED   3
+enum { GCL_TCPRXOC_OOO = 13, GCL_TCPRXOC_QUEUED, GCL_TCPRXOC_DRAINED, GCL_TCPRXOC_FREED,
+       GCL_TCPRXOC_HEADCLIP, GCL_TCPRXOC_HELD, GCL_TCPRXOC_NR = 19 };
+struct gcl_tcp_ooo_ent {   /* 16 B, 16-B aligned */
+	uint32_t seq, end;     /* m->seg_seq, m->seg_end */
+	uint32_t ref;          /* input: opaque (the mbuf's handle); output: that, or j with src 1 */
+	uint16_t flags;        /* m->flags */
+	uint16_t src;          /* output: 0 carried over from the input, 1 list entry ref of this call */
+};
+struct gcl_tcprxo_in {
+	uint32_t size, align;            /* sizeof(struct gcl_tcprxo_in) */
+	const uint32_t *order;
+	uint64_t m;
+	const uint32_t *sock;
+	const uint8_t  *l4_status;
+	const struct gcl_tcp_conn *conn;
+	uint32_t nconn;
+	uint32_t blocks;
+	const uint8_t  *rep_acks;        /* optional u8[nconn]; NULL: zeros */
+	const uint32_t *q_off;           /* optional u32[nconn + 1]; NULL: every queue is empty */
+	const struct gcl_tcp_ooo_ent *q; /* [nq] */
+	uint32_t nq;                     /* <= 2^31 */
+	uint32_t q_out_cap;              /* entries qout can hold */
+};
+struct gcl_tcprxo_out {              /* device, aligned to their element */
+	uint8_t  *oflags;                /* [m] */
+	uint16_t *skip;                  /* [m] */
+	uint8_t  *qin_state;             /* [nq] */
+	uint16_t *qin_skip, *qin_len;    /* [nq] */
+	uint64_t *qin_dst_off;           /* [nq] */
+	uint32_t *qout_off;              /* u32[nconn + 1] */
+	struct gcl_tcp_ooo_ent *qout;    /* [q_out_cap] */
+	uint64_t *totals;                /* u64[1]: the entries wanted */
+};
+int gcl_tcp_rx_ooo_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, uint32_t nq, size_t *bytes);
+int gcl_tcp_rx_ooo(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct gcl_tcprxo_in *in,
+                   const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext,
+                   const struct gcl_tcprxo_out *ooo, uint64_t *counts,
+                   void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/*
  * TCP control segments: the timer sweep, and the ACKs of a gcl_tcp_rx call.
  * Both chains end where TCP asks for a segment that carries no data.  In the
  * reference that is per-connection work on a core: tcp_worker
