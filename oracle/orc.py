@@ -18,6 +18,7 @@ REF_HOST = os.path.join(HERE, "_ref", "libhost_ref.so")
 REF_CORE = os.path.join(HERE, "_ref", "libcore_ref.so")
 REF_TRANS = os.path.join(HERE, "_ref", "libtrans_ref.so")
 REF_TCPOUT = os.path.join(HERE, "_ref", "libtcpout_ref.so")
+REF_TCPIN = os.path.join(HERE, "_ref", "libtcpin_ref.so")
 TRANS_DTYPE = np.dtype([("h5", "<u4"), ("h3", "<u4")])
 
 NR_STATS = 8
@@ -220,6 +221,73 @@ def ref_tcpout():
             if len(hdr) != 20:
                 raise ValueError("ipv4_cksum: 20 bytes")
             return l.ref_ipv4_cksum(hdr)
+    return Ref
+
+
+def ref_tcpin():
+    """The reference's own tcp_rx_conn with __tcp_rx_conn, is_acceptable,
+    tcp_rx_text and tcp_rx_append_text (runtime/net/tcp_in.c, compiled in place
+    into oracle/_ref/libtcpin_ref.so behind the driver of oracle/ref_tcpin.c),
+    or None.  The object has CONN (the names of a connection's words) and
+      run(conn, q, frames, ip_off, length) -> (trace, qfinal)
+    for one connection: @conn a dict of CONN, @q the initial rxq_ooo as (seq,
+    end, flags) rows, @frames a uint8 buffer (numpy or bytes) in which segment
+    k is the length[k] bytes at ip_off[k], its IPv4 header first.  @trace has
+    one dict per segment: the driver's record by name (pre_* before the call,
+    the PCB words after it, the event counts of the call), 'freed' (ids) and
+    'linked' ((id, bytes pulled from the front, length) of the mbufs newly at
+    the tail of c->rxq) and 'q' (the ids of rxq_ooo after the call); @qfinal is rxq_ooo after the last segment as (seq,
+    end, id).  An id is k for segment k and -1 - i for entry i of @q."""
+    if not os.path.exists(REF_TCPIN):
+        return None
+    l = ctypes.CDLL(REF_TCPIN)
+    u32, i32 = ctypes.c_uint32, ctypes.c_int32
+    l.ref_tcpin_conn_words.restype = u32
+    l.ref_tcpin_trace_words.restype = u32
+    l.ref_tcpin_run.restype = ctypes.c_int64
+    l.ref_tcpin_run.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u32, ctypes.c_char_p, ctypes.c_void_p,
+                                ctypes.c_void_p, u32, ctypes.c_void_p, ctypes.c_void_p, u32, ctypes.c_void_p, u32,
+                                ctypes.c_void_p, u32]
+    conn_words = ("snd_una", "snd_nxt", "snd_wnd", "snd_wl1", "snd_wl2", "rcv_nxt", "rcv_wnd", "rcv_mss",
+                  "snd_wscale", "acks_delayed_cnt", "ack_delayed", "rep_acks", "state", "rxq")
+    trace_words = ("pre_rcv_nxt", "pre_rcv_wnd", "pre_ooo_len", "snd_una", "snd_wnd", "snd_wl1", "snd_wl2",
+                   "rcv_nxt", "rcv_wnd", "acks_delayed_cnt", "ack_delayed", "rep_acks", "state", "ooo_len",
+                   "ack_ts", "slow", "conn_ack", "tx_ack", "pollin", "pollout", "fastrtx", "frees", "fail_err",
+                   "new_state", "rst_kind", "rst_seq", "rst_ack", "freed_at", "freed_n", "linked_at", "linked_n",
+                   "q_at", "q_n")
+    assert l.ref_tcpin_conn_words() == len(conn_words) and l.ref_tcpin_trace_words() == len(trace_words)
+
+    class Ref:
+        CONN = conn_words
+        ESTABLISHED = 2     # TCP_STATE_ESTABLISHED (runtime/net/tcp.h:41-52)
+
+        @staticmethod
+        def run(conn, q, frames, ip_off, length):
+            n, nq, nt = len(ip_off), len(q), len(trace_words)
+            frames = bytes(frames)
+            assert all(int(o) + int(k) <= len(frames) and int(k) >= 40 for o, k in zip(ip_off, length))
+            cw = (u32 * len(conn_words))(*[int(conn[f]) & 0xFFFFFFFF for f in conn_words])
+            qa = (u32 * max(3 * nq, 1))(*[int(x) & 0xFFFFFFFF for row in q for x in row])
+            off = (ctypes.c_uint64 * max(n, 1))(*[int(o) for o in ip_off])
+            ln = (u32 * max(n, 1))(*[int(k) for k in length])
+            trace = (u32 * max(nt * n, 1))()
+            cap = nq + n + 1
+            freed, linked, qfin = (i32 * cap)(), (i32 * (3 * cap))(), (u32 * (3 * cap))()
+            snap = (i32 * (cap * max(n, 1)))()
+            ret = l.ref_tcpin_run(cw, qa, nq, frames, off, ln, n, trace, freed, cap, linked, cap, snap, cap * max(n, 1),
+                                  qfin, cap)
+            if ret < 0 or ret > cap:
+                raise ValueError(f"ref_tcpin_run: {ret}")
+            res = []
+            for k in range(n):
+                t = dict(zip(trace_words, trace[nt * k:nt * (k + 1)]))
+                fa, fn, la, lk = t.pop("freed_at"), t.pop("freed_n"), t.pop("linked_at"), t.pop("linked_n")
+                t["freed"] = list(freed[fa:fa + fn])
+                t["linked"] = [tuple(linked[3 * i:3 * i + 3]) for i in range(la, la + lk)]
+                qa_, qn = t.pop("q_at"), t.pop("q_n")
+                t["q"] = list(snap[qa_:qa_ + qn])
+                res.append(t)
+            return res, [(qfin[3 * i], qfin[3 * i + 1], ctypes.c_int32(qfin[3 * i + 2]).value) for i in range(ret)]
     return Ref
 
 

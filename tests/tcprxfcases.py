@@ -3,9 +3,10 @@ cases the CPU and GPU tests share.  The model transcribes tcp_rx_conn,
 __tcp_rx_conn, is_acceptable, tcp_rx_text and tcp_rx_append_text
 (runtime/net/tcp_in.c) line by line over a dict of PCB fields, read for
 state == ESTABLISHED and an empty out-of-order queue; it knows nothing of
-csrc/gcl_tcprxf.h.  tcp_in.c cannot be compiled apart from the runtime, so the
-pin is this transcription plus the named cases below, whose expected values
-are written out by hand from the reference's lines.  What is the same as in
+csrc/gcl_tcprxf.h.  The named cases below carry expected values written out
+by hand from the reference's lines; the pin to the reference's own code is
+tests/golden/tcprx_ref.json (tests/tcprxrefcases.py), recorded from tcp_in.c
+compiled in place by oracle/ref_tcpin.c.  What is the same as in
 gcl_tcp_rx (the wraps_* comparisons, the records, the frame builders) comes
 from tests/tcprxcases.py and tests/paycases.py.
 

@@ -3,10 +3,12 @@ cases the CPU and GPU tests share.  The model transcribes tcp_rx_conn,
 __tcp_rx_conn, tcp_rx_text and tcp_rx_append_text (runtime/net/tcp_in.c) line
 by line over a dict of PCB fields and a real doubly linked list of mbuf records
 for c->rxq_ooo (list_for_each_rev, list_add_after, list_add, list_top,
-list_del); it knows nothing of csrc/gcl_tcprxo.h.  tcp_in.c cannot be compiled
-apart from the runtime, so the pin is this transcription plus the named cases
-below, whose expected values are written out by hand from the reference's
-lines.  What is the same as in gcl_tcp_rx_full (is_acceptable, the wraps_*
+list_del); it knows nothing of csrc/gcl_tcprxo.h.  The named cases below carry
+expected values written out by hand from the reference's lines; the pin to
+the reference's own code is tests/golden/tcprx_ref.json, what tcp_in.c,
+compiled in place (oracle/ref_tcpin.c), did with every segment of these cases:
+tests/tcprxrefcases.py holds this model, the host twin and the kernel to it.
+What is the same as in gcl_tcp_rx_full (is_acceptable, the wraps_*
 comparisons, the frame builders) comes from tests/tcprxfcases.py.
 
 A case is tests/tcprxfcases.py's dict plus optionally q_off (u32[nconn + 1]),
