@@ -30,7 +30,7 @@ SOURCES_HIP = ["gcl_ctx.hip", "gcl_batch.hip", "gcl_loop.hip", "gcl_xfer.hip", "
                "gcl_txq.hip"]
 SOURCES_C = ["gcl_host.c", "gcl_pcap.c", "gcl_sock.c", "gcl_neigh.c"]
 DEPS = ["gcl_device.h", "gcl_kern.h", "gcl_ctx.h", "gcl_sock.h", "gcl_pay.h", "gcl_neigh.h", "gcl_txh.h", "gcl_seg.h",
-        "gcl_tcprx.h", "gcl_tcprxf.h", "gcl_tcprxo.h", "gcl_tcptmr.h", "gcl_txq.h",
+        "gcl_tcprx.h", "gcl_tcprxf.h", "gcl_tcprxo.h", "gcl_tcprxs.h", "gcl_tcptmr.h", "gcl_txq.h",
         "../../include/gclassify.h",
         "../../include/gcl_host.h", "../../include/gcl_pcap.h"]
 SOURCE_GROUP = "gcl_group.hip"
@@ -351,6 +351,23 @@ def build_sanitized_tcprxo(out_dir=None):
     return exe
 
 
+def build_sanitized_tcprxs(out_dir=None):
+    """The same ASan + UBSan host build of csrc/gcl_host.c, linked into
+    tests/fuzz/tcprxs_fuzz.c: a stand-alone driver of gcl_tcp_rx_states_host and
+    gcl_tcp_rx_ctl_host (tcp_rx_conn in every state, and its control segments,
+    with the rules of csrc/gcl_tcprxs.h and csrc/gcl_tcptmr.h that the GPU
+    shares) over exactly sized heap arrays with random states, flags, queue
+    ranges and seg_cap.  Returns the driver's path."""
+    out_dir = out_dir or os.path.join(ROOT, "build", "sanitize")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "tcprxs_fuzz")
+    srcs = [os.path.join(ROOT, "tests", "fuzz", "tcprxs_fuzz.c"), os.path.join(CSRC, "gcl_host.c")]
+    if _stale(exe, srcs + [os.path.join(CSRC, d) for d in DEPS]):
+        _run(["gcc", "-std=gnu11", "-Wall", "-Wno-unused-parameter", *SANITIZE_FLAGS,
+              "-o", exe, *srcs, "-lm"])
+    return exe
+
+
 if __name__ == "__main__":
     if "--sanitize" in sys.argv:
         print(build_sanitized())
@@ -368,5 +385,6 @@ if __name__ == "__main__":
         print(build_sanitized_txq())
         print(build_sanitized_tcprxf())
         print(build_sanitized_tcprxo())
+        print(build_sanitized_tcprxs())
     else:
         build(force="--force" in sys.argv, verbose_resources="--resources" in sys.argv)

@@ -14,6 +14,7 @@
 #include "gcl_tcprx.h"
 #include "gcl_tcprxf.h"
 #include "gcl_tcprxo.h"
+#include "gcl_tcprxs.h"
 #include "gcl_tcptmr.h"
 #include "gcl_txq.h"
 #include "gcl_txh.h"
@@ -1159,6 +1160,304 @@ int gcl_tcp_rx_ooo_host(const struct gcl_batch *b, const struct gcl_tcprxo_in *o
 	return 0;
 }
 
+/* The rule of gcl_tcp_rx_states (gclassify.h) on the CPU: gcl_tcp_rx_ooo_host's
+ * threading and walk, every connection's live state beside its queue, composed
+ * of the pieces of gcl_tcprxs.h as the GPU walk composes them. */
+int gcl_tcp_rx_states_host(const struct gcl_batch *b, const struct gcl_tcprxs_in *sin,
+                           const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext,
+                           const struct gcl_tcprxo_out *oo, const struct gcl_tcprxs_out *so, uint64_t *counts)
+{
+	uint64_t c[GCL_TCPRXSC_NR] = {0}, at = 0;
+
+	if (!b || !sin || !out || !oo || !so || sin->size != sizeof(*sin))
+		return -EINVAL;
+	const struct gcl_tcprx_in rin = {sizeof(rin), sin->align, sin->order, sin->m, sin->sock, sin->l4_status,
+	                                 sin->conn, sin->nconn, sin->blocks};
+	const struct gcl_tcprx_in *in = &rin;
+	const uint32_t nq = sin->nq;
+
+	if (!gcl_pay_align_ok(in->align) ||
+	    (!in->order && in->m != b->n) || in->m > (1ull << 31) || in->nconn > GCL_TCPRX_MAX_CONN ||
+	    in->blocks > GCL_TCPRX_MAX_BLOCKS || !in->sock || !out->conn_off || nq > (1u << 31) || !oo->qout_off ||
+	    !oo->totals)
+		return -EINVAL;
+	if (in->nconn && (!in->conn || !out->out_conn || !out_ext || !so->state_out))
+		return -EINVAL;
+	if (in->m && (!out->verdict || !out->sflags || !out->rcv_nxt_after || !out->copy_len || !out->dst_off ||
+	              !oo->oflags || !oo->skip || !so->ev || !so->rst_seq || !so->state_after))
+		return -EINVAL;
+	if (nq && (!sin->q || !oo->qin_state || !oo->qin_skip || !oo->qin_len || !oo->qin_dst_off))
+		return -EINVAL;
+	if (sin->q_out_cap && !oo->qout)
+		return -EINVAL;
+	if (((uintptr_t)in->order & 3) || ((uintptr_t)in->sock & 3) || ((uintptr_t)in->conn & 15) ||
+	    ((uintptr_t)out->rcv_nxt_after & 3) || ((uintptr_t)out->copy_len & 1) || ((uintptr_t)out->dst_off & 7) ||
+	    ((uintptr_t)out->out_conn & 15) || ((uintptr_t)out->conn_off & 7) || ((uintptr_t)counts & 7) ||
+	    ((uintptr_t)out_ext & 15) || ((uintptr_t)sin->q_off & 3) || ((uintptr_t)sin->q & 15) ||
+	    ((uintptr_t)oo->skip & 1) || ((uintptr_t)oo->qin_skip & 1) || ((uintptr_t)oo->qin_len & 1) ||
+	    ((uintptr_t)oo->qin_dst_off & 7) || ((uintptr_t)oo->qout_off & 3) || ((uintptr_t)oo->qout & 15) ||
+	    ((uintptr_t)oo->totals & 7) || ((uintptr_t)so->rst_seq & 3))
+		return -EINVAL;
+	if (in->m && (!b->frames || b->frames_len == UINT64_MAX || b->n > (1ull << 40) ||
+	              (!b->offs && (b->stride < 16 || (b->stride & 15) || b->stride > (1u << 20))) ||
+	              !b->pkt_len || ((uintptr_t)b->pkt_len & 1)))
+		return -EINVAL;
+	const uint32_t amask = in->align ? in->align - 1 : 0;
+	/* first[k], last[k] and next[j]: connection k's segments in list order */
+	uint32_t *link = malloc(4 * ((size_t)in->m + 2 * (size_t)in->nconn) + 4);
+
+	if (!link)
+		return -ENOMEM;
+	uint32_t *first = link, *last = link + in->nconn, *next = link + 2 * (size_t)in->nconn;
+
+	for (uint32_t k = 0; k < in->nconn; k++)
+		first[k] = last[k] = GCL_TCPRX_NONE;
+	for (uint32_t i = 0; i < nq; i++) {
+		oo->qin_state[i] = GCL_OOOQ_UNTOUCHED;
+		oo->qin_skip[i] = 0;
+		oo->qin_len[i] = 0;
+		oo->qin_dst_off[i] = 0;
+	}
+	for (uint64_t j = 0; j < in->m; j++) {
+		struct gcl_tcprx_seg s = {0, 0, 0, 0, 0};
+		const uint32_t k = tcprx_entry(b, in, j, &s);
+		const uint32_t verdict = k == GCL_TCPRX_NONE ? GCL_TCPRX_NA : k >= in->nconn ? GCL_TCPRX_NOCONN :
+		                         s.len > in->conn[k].rcv_mss ? GCL_TCPRX_DROP : GCL_TCPRX_FAST;
+
+		out->verdict[j] = (uint8_t)verdict;
+		out->sflags[j] = 0;
+		out->rcv_nxt_after[j] = 0;
+		out->copy_len[j] = 0;
+		out->dst_off[j] = 0;
+		oo->oflags[j] = 0;
+		oo->skip[j] = 0;
+		so->ev[j] = 0;
+		so->rst_seq[j] = 0;
+		so->state_after[j] = 0;
+		next[j] = GCL_TCPRX_NONE;
+		if (verdict != GCL_TCPRX_FAST) {
+			c[verdict]++;
+			continue;
+		}
+		if (first[k] == GCL_TCPRX_NONE)
+			first[k] = (uint32_t)j;
+		else
+			next[last[k]] = (uint32_t)j;
+		last[k] = (uint32_t)j;
+	}
+	for (uint32_t k = 0; k < in->nconn; k++) {
+		const struct gcl_tcp_conn cn = in->conn[k];
+		struct gcl_tcp_conn_out *o = &out->out_conn[k];
+		struct gcl_tcp_conn_ext *e = &out_ext[k];
+		struct gcl_tcprxf_live x = {gcl_tcprx_live_of(&cn), sin->rep_acks ? sin->rep_acks[k] : 0, 0, 0};
+		struct tcprxo_ent Q[GCL_TCPOOO_CAP];
+		struct tcprxo_cnt n = {0, 0, 0, 0, 0, 0};
+		uint32_t qs = 0, qe = 0, qn = 0, nfast = 0, nslow = 0, nacks = 0, nrule2 = 0, ndropped = 0;
+		uint32_t first_slow = GCL_TCPRX_NONE;
+		uint32_t st = gcl_tcprxs_state_of(sin->state, k, cn.flags);
+		int dead = 0;
+
+		if (sin->q_off) {
+			qs = sin->q_off[k] < nq ? sin->q_off[k] : nq;
+			qe = sin->q_off[k + 1] < nq ? sin->q_off[k + 1] : nq;
+			if (qe < qs)
+				qe = qs;
+		}
+		const int taken = gcl_tcprxs_state_ok(st) && qe - qs <= GCL_TCPOOO_CAP;
+
+		if (taken) {
+			for (uint32_t i = qs; i < qe; i++)
+				Q[i - qs] = (struct tcprxo_ent){sin->q[i].seq, sin->q[i].end, sin->q[i].flags, i};
+			qn = qe - qs;
+		} else if (qe != qs) {
+			x.xflags |= GCL_TCPX_QSKIP;
+		}
+		for (uint32_t j = first[k]; j != GCL_TCPRX_NONE; j = next[j]) {
+			struct gcl_tcprx_seg s = {0, 0, 0, 0, 0};
+			struct gcl_tcprxs_mid mid;
+			uint32_t sf = 0, len = 0, head = 0, of = 0;
+			const uint32_t rel = x.l.rcv_nxt - in->conn[k].rcv_nxt; /* where an in-order piece lands */
+			int stop = (x.l.flags & GCL_TCPO_STOPPED) != 0 || !taken || dead;
+
+			(void)tcprx_entry(b, in, j, &s);
+			if (!stop && qn == GCL_TCPOOO_CAP) { /* would it be the 65th insert?  asked on copies: nothing moves */
+				struct gcl_tcprxf_live xt = x;
+				uint32_t stt = st, lt;
+
+				if (gcl_tcprxs_head(&cn, &xt, &stt, &s, qn, &mid, &lt) == GCL_TCPRXO_TEXT &&
+				    !gcl_tcprxo_in_order(&xt.l, s.seq))
+					stop = tcprxo_find(Q, qn, s.seq, s.seq + mid.slen) != GCL_TCPRXO_REJECT;
+			}
+			if (!stop) {
+				const uint32_t t0 = gcl_tcprxs_head(&cn, &x, &st, &s, qn, &mid, &len);
+
+				if (t0 == GCL_TCPRXO_FASTED) {
+					sf = mid.o.sf;
+				} else {
+					if (t0 == GCL_TCPRXO_TEXT) {
+						const uint32_t end = s.seq + mid.slen;
+						int used = 1, wake = 0;
+
+						if (gcl_tcprxo_in_order(&x.l, s.seq)) {
+							wake = gcl_tcprxs_in_order_wake(&x.l, s.flags);
+							if (wake && (s.flags & GCL_TCPRX_FIN))
+								mid.fin = 1;
+							gcl_tcprxs_append(&x.l, s.seq, end, (s.flags & GCL_TCPRX_FIN) != 0, &head, &len);
+							if (head) {
+								of |= GCL_OOOF_HEADCLIP;
+								n.headclip++;
+							}
+						} else {
+							const uint32_t pos = tcprxo_find(Q, qn, s.seq, end);
+
+							of |= GCL_OOOF_OOO;
+							n.ooo++;
+							if (pos == GCL_TCPRXO_REJECT) {
+								used = 0;
+							} else {
+								memmove(&Q[pos + 1], &Q[pos], (qn - pos) * sizeof(Q[0]));
+								Q[pos] = (struct tcprxo_ent){s.seq, end, s.flags | 1u << 16, j};
+								qn++;
+								of |= GCL_OOOF_QUEUED;
+								n.queued++;
+							}
+						}
+						while (used && qn) {
+							const uint32_t t = gcl_tcprxo_drain_test(Q[0].seq, Q[0].end, x.l.rcv_nxt);
+							uint32_t h = 0, ln = 0;
+							const uint32_t r = x.l.rcv_nxt - in->conn[k].rcv_nxt;
+
+							if (t == GCL_TCPRXO_BREAK)
+								break;
+							if (t == GCL_TCPRXO_APPEND) {
+								wake = 1;
+								if (Q[0].fl & GCL_TCPRX_FIN)
+									mid.fin = 1;
+								gcl_tcprxs_append(&x.l, Q[0].seq, Q[0].end, (Q[0].fl & GCL_TCPRX_FIN) != 0, &h, &ln);
+								n.headclip += h != 0;
+								n.drained++;
+							} else {
+								n.freed++;
+							}
+							tcprxo_fate(out, oo, &Q[0], t, h, ln, r);
+							memmove(&Q[0], &Q[1], (qn - 1) * sizeof(Q[0]));
+							qn--;
+						}
+						gcl_tcprxo_text_tail(&x.l, &mid.o, used, wake, qn);
+						gcl_tcprxs_fin(&x, &st, &mid);
+					}
+					sf = gcl_tcprxo_done(&x.l, &mid.o);
+				}
+			}
+			if (stop) {
+				if (!(x.l.flags & GCL_TCPO_STOPPED))
+					first_slow = j;
+				x.l.flags |= GCL_TCPO_STOPPED;
+				nslow++;
+				out->verdict[j] = GCL_TCPRX_SLOW;
+				c[GCL_TCPRX_SLOW]++;
+				continue;
+			}
+			dead = gcl_tcprxs_ends(mid.ev);
+			nfast++;
+			nacks += (sf & GCL_TCPRX_SF_ACK_NOW) != 0;
+			nrule2 += (sf & GCL_TCPRX_SF_RULE2) != 0;
+			ndropped += (sf & GCL_TCPRX_SF_DROPPED) != 0;
+			c[GCL_TCPRX_FAST]++;
+			c[GCL_TCPRXC_WAKES] += (sf & GCL_TCPRX_SF_WAKE) != 0;
+			c[GCL_TCPRXFC_TXWAKES] += (sf & GCL_TCPRX_SF_TXWAKE) != 0;
+			c[GCL_TCPRXFC_FASTRTX] += (sf & GCL_TCPRX_SF_FASTRTX) != 0;
+			c[GCL_TCPRXFC_DUPACKS] += (sf & GCL_TCPRXF_EV_DUPACK) != 0;
+			c[GCL_TCPRXSC_RSTS] += (mid.ev & (GCL_TCPS_RST | GCL_TCPS_RST_ACK)) != 0;
+			c[GCL_TCPRXSC_FAILS] += (mid.ev & GCL_TCPS_FAIL) != 0;
+			c[GCL_TCPRXSC_FINS] += (mid.ev & GCL_TCPS_FIN) != 0;
+			c[GCL_TCPRXSC_STATE_CHANGES] += (mid.ev & GCL_TCPS_STATE) != 0;
+			out->sflags[j] = (uint8_t)sf;
+			out->rcv_nxt_after[j] = x.l.rcv_nxt;
+			so->ev[j] = (uint8_t)mid.ev;
+			so->rst_seq[j] = mid.rst_seq;
+			so->state_after[j] = (uint8_t)st;
+			if (!(of & GCL_OOOF_QUEUED)) { /* a queued entry gets these with its fate */
+				out->copy_len[j] = (uint16_t)len;
+				out->dst_off[j] = len ? rel : 0;
+				oo->oflags[j] = (uint8_t)of;
+				oo->skip[j] = (uint16_t)head;
+			}
+		}
+		for (uint32_t i = 0; i < qn; i++) {
+			if (Q[i].fl >> 16) {
+				oo->oflags[Q[i].idx] = GCL_OOOF_OOO | GCL_OOOF_QUEUED | GCL_OOOF_HELD;
+				n.held++;
+			} else {
+				oo->qin_state[Q[i].idx] = GCL_OOOQ_KEPT;
+			}
+			if (at + i < sin->q_out_cap)
+				oo->qout[at + i] = (struct gcl_tcp_ooo_ent){Q[i].seq, Q[i].end,
+				                                            Q[i].fl >> 16 ? Q[i].idx : sin->q[Q[i].idx].ref,
+				                                            (uint16_t)Q[i].fl, (uint16_t)(Q[i].fl >> 16)};
+		}
+		oo->qout_off[k] = (uint32_t)at;
+		at += qn;
+		memset(o, 0, sizeof(*o));
+		o->snd_una = x.l.snd_una;
+		o->snd_wnd = x.l.snd_wnd;
+		o->snd_wl1 = x.l.snd_wl1;
+		o->snd_wl2 = x.l.snd_wl2;
+		o->rcv_nxt = x.l.rcv_nxt;
+		o->rcv_wnd = x.l.rcv_wnd;
+		o->nfast = nfast;
+		o->nslow = nslow;
+		o->nacks = nacks;
+		o->first_slow = first_slow;
+		o->acks_delayed_cnt = (uint8_t)x.l.cnt;
+		o->flags = (uint8_t)x.l.flags;
+		memset(e, 0, sizeof(*e));
+		e->nrule2 = nrule2;
+		e->ndropped = ndropped;
+		e->fast_rtx_ack = x.fast_rtx_ack;
+		e->rep_acks = (uint8_t)x.rep_acks;
+		e->xflags = (uint8_t)x.xflags;
+		so->state_out[k] = (uint8_t)st;
+		c[GCL_TCPRXC_BYTES] += (uint32_t)(x.l.rcv_nxt - in->conn[k].rcv_nxt);
+		c[GCL_TCPRXC_ACKS] += nacks;
+		c[GCL_TCPRXFC_RULE2] += nrule2;
+		c[GCL_TCPRXFC_DROPPED] += ndropped;
+		c[GCL_TCPRXOC_OOO] += n.ooo;
+		c[GCL_TCPRXOC_QUEUED] += n.queued;
+		c[GCL_TCPRXOC_DRAINED] += n.drained;
+		c[GCL_TCPRXOC_FREED] += n.freed;
+		c[GCL_TCPRXOC_HEADCLIP] += n.headclip;
+		c[GCL_TCPRXOC_HELD] += n.held;
+	}
+	oo->qout_off[in->nconn] = (uint32_t)at;
+	oo->totals[0] = at;
+	at = 0;
+	for (uint32_t k = 0; k < in->nconn; k++) {
+		out->conn_off[k] = at;
+		at += gcl_tcprx_pad((uint32_t)(out->out_conn[k].rcv_nxt - in->conn[k].rcv_nxt), amask);
+	}
+	out->conn_off[in->nconn] = at;
+	/* the layout: every accepted piece moves by its connection's offset */
+	for (uint32_t k = 0; k < in->nconn; k++) {
+		for (uint32_t j = first[k]; j != GCL_TCPRX_NONE; j = next[j])
+			if (out->copy_len[j])
+				out->dst_off[j] += out->conn_off[k];
+		if (sin->q_off && gcl_tcprxs_state_ok(gcl_tcprxs_state_of(sin->state, k, in->conn[k].flags))) {
+			const uint32_t qs = sin->q_off[k] < nq ? sin->q_off[k] : nq;
+			const uint32_t qe = sin->q_off[k + 1] < nq ? sin->q_off[k + 1] : nq;
+
+			for (uint32_t i = qs; i < qe && qe - qs <= GCL_TCPOOO_CAP; i++)
+				if (oo->qin_state[i] == GCL_OOOQ_DRAINED && oo->qin_len[i])
+					oo->qin_dst_off[i] += out->conn_off[k];
+		}
+	}
+	free(link);
+	if (counts)
+		for (int k = 0; k < GCL_TCPRXSC_NR; k++)
+			counts[k] += c[k];
+	return 0;
+}
+
 /* what gcl_tcp_tick and gcl_tcp_rx_acks both refuse of the fields they share */
 static int ctl_refused(uint32_t nconn, uint32_t blocks, uint64_t seg_cap, uint32_t frame_stride, uint64_t items,
                        const struct gcl_ctlseg_out *o, const uint64_t *counts)
@@ -1263,6 +1562,63 @@ int gcl_tcp_rx_acks_host(const struct gcl_rxack_in *in, const struct gcl_ctlseg_
 		const uint32_t after = in->rcv_nxt_after[j];
 		(void)ctl_emit(out, at, in->seg_cap, in->frame_base, in->frame_stride, cn, &in->addr[k], k, GCL_CTL_ACK,
 		               (uint32_t)j, after, gcl_rxack_wnd(cn->rcv_wnd, cn->rcv_nxt, after));
+		at++;
+	}
+	out->totals[0] = at;
+	out->totals[1] = at < in->seg_cap ? at : in->seg_cap;
+	if (counts) {
+		counts[GCL_RXACKC_WANTED] += at;
+		counts[GCL_RXACKC_WRITTEN] += out->totals[1];
+		counts[GCL_RXACKC_SKIPPED] += skipped;
+	}
+	return 0;
+}
+
+/* The rule of gcl_tcp_rx_ctl (gclassify.h) on the CPU: gcl_tcp_rx_acks_host's
+ * walk with gcl_rxctl_kind of gcl_tcptmr.h saying which segment an entry asks for. */
+int gcl_tcp_rx_ctl_host(const struct gcl_rxctl_in *in, const struct gcl_ctlseg_out *out, uint64_t *counts)
+{
+	uint64_t at = 0, skipped = 0;
+
+	if (!in || !out || in->size != sizeof(*in) || in->m > (1ull << 31) ||
+	    ctl_refused(in->nconn, in->blocks, in->seg_cap, in->frame_stride, in->m, out, counts))
+		return -EINVAL;
+	if (in->m && (!in->sock || !in->verdict || !in->sflags || !in->rcv_nxt_after || !in->ev || !in->rst_seq))
+		return -EINVAL;
+	if (in->m && in->nconn && (!in->conn || !in->addr))
+		return -EINVAL;
+	if (((uintptr_t)in->order & 3) || ((uintptr_t)in->sock & 3) || ((uintptr_t)in->rcv_nxt_after & 3) ||
+	    ((uintptr_t)in->conn & 15) || ((uintptr_t)in->addr & 15) || ((uintptr_t)in->rst_seq & 3))
+		return -EINVAL;
+	for (uint64_t j = 0; j < in->m; j++) {
+		const uint32_t kind = gcl_rxctl_kind(in->verdict[j], in->sflags[j], in->ev[j]);
+
+		if (kind == GCL_RXCTL_NONE)
+			continue;
+		const uint64_t i = in->order ? in->order[j] : j;
+		const uint32_t k = i < in->n ? in->sock[i] : UINT32_MAX;
+
+		if (k >= in->nconn) {
+			skipped++;
+			continue;
+		}
+		const struct gcl_tcp_conn *cn = &in->conn[k];
+
+		if (kind == GCL_CTL_ACK) {
+			const uint32_t after = in->rcv_nxt_after[j];
+			(void)ctl_emit(out, at, in->seg_cap, in->frame_base, in->frame_stride, cn, &in->addr[k], k, GCL_CTL_ACK,
+			               (uint32_t)j, after, gcl_rxack_wnd(cn->rcv_wnd, cn->rcv_nxt, after));
+		} else if (at < in->seg_cap) {
+			uint32_t a[4], d[8];
+
+			memcpy(a, &in->addr[k], sizeof(a)); /* little-endian host */
+			gcl_ctl_rst_desc(a, kind, in->rst_seq[j], d);
+			memcpy(&out->desc[at], d, sizeof(out->desc[at]));
+			out->frame_off[at] = in->frame_base + at * in->frame_stride;
+			out->seg_conn[at] = k;
+			out->seg_kind[at] = (uint8_t)kind;
+			out->seg_src[at] = (uint32_t)j;
+		}
 		at++;
 	}
 	out->totals[0] = at;

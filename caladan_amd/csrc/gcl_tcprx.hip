@@ -70,6 +70,7 @@
 #include "gcl_tcprx.h"
 #include "gcl_tcprxf.h"
 #include "gcl_tcprxo.h"
+#include "gcl_tcprxs.h"
 
 namespace gclk {
 
@@ -1081,6 +1082,287 @@ __global__ void __launch_bounds__(kRxThreads) rxo_walk_kernel(RxoParams p, const
 	}
 }
 
+/* ---- gcl_tcp_rx_states: gcl_tcp_rx_ooo's walk with the live state; every other launch is gcl_tcp_rx_ooo's ---- */
+
+struct RxsParams {
+	RxoParams o;
+	const uint8_t *state;   /* [nconn] or NULL */
+	uint8_t *ev;            /* [m] */
+	uint32_t *rst_seq;      /* [m] */
+	uint8_t *state_after;   /* [m] */
+	uint8_t *state_out;     /* [nconn] */
+};
+
+/*
+ * rxo_walk_kernel with one more wave-uniform register, the live state @st, and
+ * the rule of gcl_tcprxs.h: one wave per connection, serial and wave-uniform
+ * over each 64-segment chunk, the queue in the lanes.  The FIN of a popped
+ * entry is its flags word at lane 0.  Whether a segment's insert would be the
+ * 65th is asked on copies of the live words, so a stop leaves them untouched.
+ * A known cost: while a connection's queue holds 64 entries every one of its
+ * segments runs gcl_tcprxs_head twice, once on the copies and once for real.
+ *
+ * Store order is rxo_walk_kernel's: copy_len, dst_off, oflags and skip of a
+ * QUEUED entry are stored once, with its fate.  ev, rst_seq and state_after of
+ * an entry are final when the entry has been processed and only the chunk's
+ * own store writes them.  No two stores of this kernel hit one address and no
+ * fence is needed.  The four counters this call adds are summed per connection
+ * here and added to counts by lane 0: atomics that only add.
+ */
+__global__ void __launch_bounds__(kRxThreads) rxs_walk_kernel(RxsParams ps, const uint32_t *sorted)
+{
+	const RxoParams &p = ps.o;
+	const RxParams &k = p.f.k;
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRxWaves + (threadIdx.x >> 6)));
+
+	if (c >= k.nconn)
+		return;
+	struct gcl_tcp_conn cn;
+	{
+		const uint4 a = k.conn[3 * (size_t)c], b = k.conn[3 * (size_t)c + 1], d = k.conn[3 * (size_t)c + 2];
+		cn.snd_una = a.x; cn.snd_nxt = a.y; cn.snd_wnd = a.z; cn.snd_wl1 = a.w;
+		cn.snd_wl2 = b.x; cn.rcv_nxt = b.y; cn.rcv_wnd = b.z;
+		cn.rcv_mss = (uint16_t)b.w; cn.snd_wscale = (uint8_t)(b.w >> 16); cn.flags = (uint8_t)(b.w >> 24);
+		cn.acks_delayed_cnt = (uint8_t)d.x;
+	}
+	struct gcl_tcprxf_live x;
+	x.l = gcl_tcprx_live_of(&cn);
+	x.rep_acks = p.f.rep_acks ? p.f.rep_acks[c] : 0;
+	x.fast_rtx_ack = 0;
+	x.xflags = 0;
+	uint32_t st = (uint32_t)__builtin_amdgcn_readfirstlane((int)gcl_tcprxs_state_of(ps.state, c, cn.flags));
+	const uint32_t rcv0 = cn.rcv_nxt;
+	uint32_t qs, qe;
+	rxo_range(p, c, &qs, &qe);
+	const uint32_t nin = qe - qs;
+	const bool taken = gcl_tcprxs_state_ok(st) && nin <= GCL_TCPOOO_CAP;
+	RxoEnt e = {0, 0, 0, 0};
+	if (taken && lane < nin) {
+		const uint4 w = p.q[qs + lane];
+		e.seq = w.x;
+		e.end = w.y;
+		e.fl = w.w & 0xFFFFu;
+		e.idx = qs + lane;
+	}
+	uint32_t qn = taken ? nin : 0;
+	if (!taken && nin)
+		x.xflags |= GCL_TCPX_QSKIP;
+
+	const uint2 rn = k.run[c];
+	const uint64_t re = rn.y < k.m ? rn.y : k.m;
+	const uint64_t rs = rn.x < re ? rn.x : re;
+	uint32_t nfast = 0, nslow = 0, nacks = 0, wakes = 0, first_slow = GCL_TCPRX_NONE;
+	uint32_t nrule2 = 0, ndropped = 0, ntxw = 0, nfrtx = 0, ndup = 0;
+	uint32_t nooo = 0, nqueued = 0, ndrained = 0, nfreed = 0, nhead = 0;
+	uint32_t nrst = 0, nfail = 0, nfin = 0, nstate = 0;
+	bool dead = false; /* a FAIL or a PUT went by: the next segment stops */
+
+	for (uint64_t base = rs; base < re; base += 64) { /* uniform */
+		const uint32_t nv = re - base < 64 ? (uint32_t)(re - base) : 64;
+		const bool valid = lane < nv;
+		uint32_t j = valid ? sorted[base + lane] : 0;
+		if (j >= k.m)
+			j = (uint32_t)(k.m - 1);
+		const uint4 rec = valid ? k.rec[j] : make_uint4(0, 0, 0, 0);
+		const bool stopped = (x.l.flags & GCL_TCPO_STOPPED) != 0;
+		uint32_t H = 0, sf_mine = 0, after_mine = 0, copy_mine = 0, head_mine = 0, of_mine = 0, rel_mine = 0;
+		uint32_t ev_mine = 0, rseq_mine = 0, st_mine = 0;
+
+		if (!stopped && taken) {
+			H = nv;
+			for (uint32_t at = 0; at < nv; at++) { /* uniform */
+				const uint32_t z = rx_lane(rec.z, at);
+				const struct gcl_tcprx_seg s = {rx_lane(rec.x, at), rx_lane(rec.y, at), z & 0xFFFFu,
+				                                rx_lane(rec.w, at), z >> 16};
+				const uint32_t jj = rx_lane(j, at);
+				const uint32_t rel = x.l.rcv_nxt - rcv0; /* where an in-order piece lands */
+				struct gcl_tcprxs_mid mid;
+				uint32_t sf = 0, len = 0, head = 0, of = 0;
+				bool stop = dead;
+
+				mid.ev = 0;
+				mid.rst_seq = 0;
+				if (!stop && qn == GCL_TCPOOO_CAP) { /* would it be the 65th insert?  asked on copies: nothing moves */
+					struct gcl_tcprxf_live xt = x;
+					uint32_t stt = st, lt;
+
+					if (gcl_tcprxs_head(&cn, &xt, &stt, &s, qn, &mid, &lt) == GCL_TCPRXO_TEXT &&
+					    !gcl_tcprxo_in_order(&xt.l, s.seq))
+						stop = rxo_find(e, qn, lane, s.seq, s.seq + mid.slen) != GCL_TCPRXO_REJECT;
+				}
+				if (!stop) {
+					const uint32_t t0 = gcl_tcprxs_head(&cn, &x, &st, &s, qn, &mid, &len);
+
+					if (t0 == GCL_TCPRXO_FASTED) {
+						sf = mid.o.sf;
+					} else {
+						if (t0 == GCL_TCPRXO_TEXT) {
+							const uint32_t end = s.seq + mid.slen;
+							int used = 1, wake = 0;
+
+							if (gcl_tcprxo_in_order(&x.l, s.seq)) {
+								wake = gcl_tcprxs_in_order_wake(&x.l, s.flags);
+								if (wake && (s.flags & GCL_TCPRX_FIN))
+									mid.fin = 1;
+								gcl_tcprxs_append(&x.l, s.seq, end, (s.flags & GCL_TCPRX_FIN) != 0, &head, &len);
+								if (head) {
+									of |= GCL_OOOF_HEADCLIP;
+									nhead++;
+								}
+							} else {
+								const uint32_t pos = rxo_find(e, qn, lane, s.seq, end);
+
+								of |= GCL_OOOF_OOO;
+								nooo++;
+								if (pos == GCL_TCPRXO_REJECT) {
+									used = 0;
+								} else { /* the lanes at and above pos move up by one; qn < 64 here */
+									const RxoEnt u = {(uint32_t)__shfl_up((int)e.seq, 1), (uint32_t)__shfl_up((int)e.end, 1),
+									                  (uint32_t)__shfl_up((int)e.fl, 1), (uint32_t)__shfl_up((int)e.idx, 1)};
+									if (lane > pos)
+										e = u;
+									if (lane == pos) {
+										e.seq = s.seq;
+										e.end = end;
+										e.fl = s.flags | 1u << 16;
+										e.idx = jj;
+									}
+									qn++;
+									of |= GCL_OOOF_QUEUED;
+									nqueued++;
+								}
+							}
+							while (used && qn) { /* uniform: the drain reads lane 0 */
+								const uint32_t hs = rx_lane(e.seq, 0), he = rx_lane(e.end, 0);
+								const uint32_t hf = rx_lane(e.fl, 0), hi = rx_lane(e.idx, 0);
+								const uint32_t t = gcl_tcprxo_drain_test(hs, he, x.l.rcv_nxt);
+								const uint32_t r = x.l.rcv_nxt - rcv0;
+								uint32_t h = 0, ln = 0;
+
+								if (t == GCL_TCPRXO_BREAK)
+									break;
+								if (t == GCL_TCPRXO_APPEND) {
+									wake = 1;
+									if (hf & GCL_TCPRX_FIN)
+										mid.fin = 1;
+									gcl_tcprxs_append(&x.l, hs, he, (hf & GCL_TCPRX_FIN) != 0, &h, &ln);
+									nhead += h != 0;
+									ndrained++;
+								} else {
+									nfreed++;
+								}
+								if (lane == 0)
+									rxo_fate(p, hf, hi, t, h, ln, r);
+								e.seq = (uint32_t)__shfl_down((int)e.seq, 1);
+								e.end = (uint32_t)__shfl_down((int)e.end, 1);
+								e.fl = (uint32_t)__shfl_down((int)e.fl, 1);
+								e.idx = (uint32_t)__shfl_down((int)e.idx, 1);
+								qn--;
+							}
+							gcl_tcprxo_text_tail(&x.l, &mid.o, used, wake, qn);
+							gcl_tcprxs_fin(&x, &st, &mid);
+						}
+						sf = gcl_tcprxo_done(&x.l, &mid.o);
+					}
+				}
+				if (stop) {
+					H = at;
+					break;
+				}
+				dead = gcl_tcprxs_ends(mid.ev);
+				nrst += (mid.ev & (GCL_TCPS_RST | GCL_TCPS_RST_ACK)) != 0;
+				nfail += (mid.ev & GCL_TCPS_FAIL) != 0;
+				nfin += (mid.ev & GCL_TCPS_FIN) != 0;
+				nstate += (mid.ev & GCL_TCPS_STATE) != 0;
+				if (lane == at) {
+					sf_mine = sf;
+					after_mine = x.l.rcv_nxt;
+					copy_mine = len;
+					head_mine = head;
+					of_mine = of;
+					rel_mine = rel;
+					ev_mine = mid.ev;
+					rseq_mine = mid.rst_seq;
+					st_mine = st;
+				}
+			}
+		}
+		nfast += H;
+		nslow += nv - H;
+		if (H < nv) {
+			if (!stopped)
+				first_slow = rx_lane(j, H);
+			x.l.flags |= GCL_TCPO_STOPPED;
+		}
+		if (H) { /* lanes at and past H hold 0 */
+			nacks += rx_pop(sf_mine & GCL_TCPRX_SF_ACK_NOW);
+			wakes += rx_pop(sf_mine & GCL_TCPRX_SF_WAKE);
+			nrule2 += rx_pop(sf_mine & GCL_TCPRX_SF_RULE2);
+			ndropped += rx_pop(sf_mine & GCL_TCPRX_SF_DROPPED);
+			ntxw += rx_pop(sf_mine & GCL_TCPRX_SF_TXWAKE);
+			nfrtx += rx_pop(sf_mine & GCL_TCPRX_SF_FASTRTX);
+			ndup += rx_pop(sf_mine & GCL_TCPRXF_EV_DUPACK);
+		}
+		if (valid) {
+			k.verdict[j] = (uint8_t)(lane < H ? GCL_TCPRX_FAST : GCL_TCPRX_SLOW);
+			k.sflags[j] = (uint8_t)sf_mine;
+			k.after[j] = after_mine;
+			ps.ev[j] = (uint8_t)ev_mine;
+			ps.rst_seq[j] = rseq_mine;
+			ps.state_after[j] = (uint8_t)st_mine;
+			if (!(of_mine & GCL_OOOF_QUEUED)) { /* a queued entry gets these with its fate */
+				k.copy_len[j] = (uint16_t)copy_mine;
+				k.dst_off[j] = copy_mine ? rel_mine : 0; /* layout adds conn_off[c] */
+				p.oflags[j] = (uint8_t)of_mine;
+				p.skip[j] = (uint16_t)head_mine;
+			}
+		}
+	}
+	/* the queue as it stands: HELD and KEPT, and the entries staged for rxo_qout_kernel */
+	const bool staged = rs < re;
+	const bool mine = lane < qn, held = mine && (e.fl >> 16) != 0;
+	const uint64_t heldmask = __ballot(held);
+	const uint32_t rank_l = (uint32_t)__popcll(heldmask & ((1ull << lane) - 1)), rank_q = lane - rank_l;
+	if (mine) {
+		uint32_t ref = e.idx;
+		if (held) {
+			k.copy_len[e.idx] = 0;
+			k.dst_off[e.idx] = 0;
+			p.oflags[e.idx] = GCL_OOOF_OOO | GCL_OOOF_QUEUED | GCL_OOOF_HELD;
+			p.skip[e.idx] = 0;
+		} else {
+			p.qin_state[e.idx] = GCL_OOOQ_KEPT;
+			ref = p.q[e.idx].z;
+		}
+		if (staged) /* rank_q < qe - qs and rank_l < re - rs: below nq, and below nq + m */
+			p.stage[held ? (size_t)p.nq + rs + rank_l : (size_t)qs + rank_q] = make_uint4(e.seq, e.end, ref, e.fl);
+	}
+	const uint32_t nheld = (uint32_t)__popcll(heldmask);
+	if (lane == 0) {
+		k.out_conn[3 * (size_t)c] = make_uint4(x.l.snd_una, x.l.snd_wnd, x.l.snd_wl1, x.l.snd_wl2);
+		k.out_conn[3 * (size_t)c + 1] = make_uint4(x.l.rcv_nxt, x.l.rcv_wnd, nfast, nslow);
+		k.out_conn[3 * (size_t)c + 2] = make_uint4(nacks, first_slow, (x.l.cnt & 0xFFu) | (x.l.flags & 0xFFu) << 8, 0);
+		p.f.out_ext[c] = make_uint4(nrule2, ndropped, x.fast_rtx_ack, (x.rep_acks & 0xFFu) | (x.xflags & 0xFFu) << 8);
+		p.f.xcnt[c] = make_uint4(ntxw, nfrtx, ndup, nooo);
+		p.ocnt[c] = make_uint4(nqueued, ndrained, nfreed, nhead);
+		p.qmeta[c] = make_uint4(qn | (uint32_t)staged << 8 | (uint32_t)taken << 9, nheld, (uint32_t)heldmask,
+		                        (uint32_t)(heldmask >> 32));
+		k.wakes[c] = wakes;
+		ps.state_out[c] = (uint8_t)st;
+		if (k.counts) {
+			if (nrst)
+				atomicAdd(k.counts + GCL_TCPRXSC_RSTS, (unsigned long long)nrst);
+			if (nfail)
+				atomicAdd(k.counts + GCL_TCPRXSC_FAILS, (unsigned long long)nfail);
+			if (nfin)
+				atomicAdd(k.counts + GCL_TCPRXSC_FINS, (unsigned long long)nfin);
+			if (nstate)
+				atomicAdd(k.counts + GCL_TCPRXSC_STATE_CHANGES, (unsigned long long)nstate);
+		}
+	}
+}
+
 /*
  * One wave per connection, after the scans: lane i writes entry i of the final
  * queue to qout (from the stage, or straight from q for a connection that had
@@ -1261,6 +1543,12 @@ struct RxFull {
 struct RxOoo {
 	const struct gcl_tcprxo_in *in;
 	const struct gcl_tcprxo_out *out;
+};
+
+/* what gcl_tcp_rx_states adds to a gcl_tcp_rx_ooo call; NULL: not that call */
+struct RxStates {
+	const uint8_t *state;
+	const struct gcl_tcprxs_out *out;
 };
 
 /* the bytes gcl_tcp_rx_ooo keeps behind gcl_tcp_rx_full's workspace: ocnt, qmeta, qsum, stage */
@@ -1479,6 +1767,224 @@ static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl
 	return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 
+/*
+ * gcl_tcp_rx_states' own driver: rx_run as gcl_tcp_rx_ooo takes it, with the
+ * three arrays of @sts cleared and rxs_walk_kernel in rxo_walk_kernel's place.
+ * rx_run itself, which the three older calls share, is left as it was.
+ */
+static int rxs_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprx_in *in,
+                  const struct gcl_tcprx_out *out, const RxFull *full, const RxOoo *ooo, const RxStates *sts,
+                  uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+	hipStream_t s = (hipStream_t)hip_stream;
+	RxGeom g;
+
+	if (!full || !ooo || !sts || !ooo->in)
+		return -EINVAL;
+	if (!c || !b || !in || !out || in->size != sizeof(*in) || !gcl_pay_align_ok(in->align) ||
+	    (!in->order && in->m != b->n) || rx_geometry(in->m, in->nconn, in->blocks, &g) || !in->sock ||
+	    !out->conn_off)
+		return -EINVAL;
+	if (in->nconn && (!in->conn || !out->out_conn || !full->out_ext))
+		return -EINVAL;
+	if (rx_misaligned(full->out_ext, 16))
+		return -EINVAL;
+	if (in->m && (!out->verdict || !out->sflags || !out->rcv_nxt_after || !out->copy_len || !out->dst_off))
+		return -EINVAL;
+	if (rx_misaligned(in->order, 4) || rx_misaligned(in->sock, 4) || rx_misaligned(in->conn, 16) ||
+	    rx_misaligned(out->rcv_nxt_after, 4) || rx_misaligned(out->copy_len, 2) ||
+	    rx_misaligned(out->dst_off, 8) || rx_misaligned(out->out_conn, 16) ||
+	    rx_misaligned(out->conn_off, 8) || rx_misaligned(counts, 8))
+		return -EINVAL;
+	{
+		const struct gcl_tcprxo_in *oi = ooo->in;
+		const struct gcl_tcprxo_out *oo = ooo->out;
+
+		if (!oo || oi->nq > (1u << 31) || !oo->qout_off || !oo->totals || (in->m && (!oo->oflags || !oo->skip)) ||
+		    (oi->nq && (!oi->q || !oo->qin_state || !oo->qin_skip || !oo->qin_len || !oo->qin_dst_off)) ||
+		    (oi->q_out_cap && !oo->qout))
+			return -EINVAL;
+		if (rx_misaligned(oi->q_off, 4) || rx_misaligned(oi->q, 16) || rx_misaligned(oo->skip, 2) ||
+		    rx_misaligned(oo->qin_skip, 2) || rx_misaligned(oo->qin_len, 2) || rx_misaligned(oo->qin_dst_off, 8) ||
+		    rx_misaligned(oo->qout_off, 4) || rx_misaligned(oo->qout, 16) || rx_misaligned(oo->totals, 8))
+			return -EINVAL;
+	}
+	{
+		const struct gcl_tcprxs_out *so = sts->out;
+
+		if (!so || (in->m && (!so->ev || !so->rst_seq || !so->state_after)) ||
+		    (in->nconn && !so->state_out) || rx_misaligned(so->rst_seq, 4))
+			return -EINVAL;
+	}
+	/* gcl_tcp_rx_full keeps xcnt behind gcl_tcp_rx's workspace, gcl_tcp_rx_ooo its own behind that */
+	const size_t xbytes = 16 * (size_t)in->nconn + rxo_extra(in->m, in->nconn, ooo->in->nq);
+	if (!workspace || rx_misaligned(workspace, 16) || workspace_bytes < g.bytes + xbytes)
+		return -EINVAL;
+	if (in->m && (!b->frames || b->frames_len == UINT64_MAX || b->n > (1ull << 40) ||
+	              (!b->offs && (b->stride < 16 || (b->stride & 15) || b->stride > (1u << 20))) ||
+	              !b->pkt_len || rx_misaligned(b->pkt_len, 2)))
+		return -EINVAL;
+	if (hipSetDevice(c->device) != hipSuccess)
+		return -EIO;
+	c->last_stream = s;
+
+	uint8_t *ws = (uint8_t *)workspace;
+	RxParams k;
+	k.frames = b->frames;
+	k.frames_len = b->frames_len;
+	k.stride = b->stride;
+	k.offs = b->offs;
+	k.pkt_len = b->pkt_len;
+	k.n = b->n;
+	k.order = in->order;
+	k.sock = in->sock;
+	k.l4_status = in->l4_status;
+	k.conn = (const uint4 *)in->conn;
+	k.verdict = out->verdict;
+	k.sflags = out->sflags;
+	k.after = out->rcv_nxt_after;
+	k.copy_len = out->copy_len;
+	k.dst_off = out->dst_off;
+	k.out_conn = (uint4 *)out->out_conn;
+	k.conn_off = (unsigned long long *)out->conn_off;
+	k.counts = (unsigned long long *)counts;
+	k.rec = (uint4 *)(ws + g.rec);
+	k.cookie = (uint32_t *)(ws + g.cookie);
+	k.idx[0] = (uint32_t *)(ws + g.idx[0]);
+	k.idx[1] = (uint32_t *)(ws + g.idx[1]);
+	k.hist = (uint32_t *)(ws + g.hist);
+	k.csum = (uint32_t *)(ws + g.csum);
+	k.lsum = (unsigned long long *)(ws + g.lsum);
+	k.tot = (uint32_t *)(ws + g.tot);
+	k.run = (uint2 *)(ws + g.run);
+	k.wakes = (uint32_t *)(ws + g.wakes);
+	k.m = in->m;
+	k.nconn = in->nconn;
+	k.amask = in->align ? in->align - 1 : 0;
+
+	const uint32_t cus = (uint32_t)(c->num_cus > 0 ? c->num_cus : 1);
+	const uint64_t tiles = (in->m + kRxThreads - 1) / kRxThreads;
+	const unsigned egrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)cus * 8));
+	k.ranges = in->blocks ? in->blocks :
+	           (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(tiles, std::min<uint32_t>(cus * kRxBlocksPerCu,
+	                                                                                      GCL_TCPRX_MAX_BLOCKS)));
+	k.range_len = (uint32_t)(((in->m + k.ranges - 1) / k.ranges + 63) / 64 * 64);
+	if (k.range_len == 0)
+		k.range_len = 64;
+
+	{ /* what no walk may reach: entries that are NA, NOCONN or DROP, queue entries of no taken connection */
+		const struct gcl_tcprxo_out *oo = ooo->out;
+		const size_t nq = ooo->in->nq;
+
+		if ((in->m && (hipMemsetAsync(oo->oflags, 0, in->m, s) != hipSuccess ||
+		               hipMemsetAsync(oo->skip, 0, 2 * (size_t)in->m, s) != hipSuccess)) ||
+		    (nq && (hipMemsetAsync(oo->qin_state, GCL_OOOQ_UNTOUCHED, nq, s) != hipSuccess ||
+		            hipMemsetAsync(oo->qin_skip, 0, 2 * nq, s) != hipSuccess ||
+		            hipMemsetAsync(oo->qin_len, 0, 2 * nq, s) != hipSuccess ||
+		            hipMemsetAsync(oo->qin_dst_off, 0, 8 * nq, s) != hipSuccess)))
+			return -EIO;
+		if (in->nconn == 0 && (hipMemsetAsync(oo->qout_off, 0, 4, s) != hipSuccess ||
+		                       hipMemsetAsync(oo->totals, 0, 8, s) != hipSuccess))
+			return -EIO;
+	}
+	if (in->m) { /* NA, NOCONN and DROP entries, and with nconn == 0 every entry */
+		const struct gcl_tcprxs_out *so = sts->out;
+
+		if (hipMemsetAsync(so->ev, 0, in->m, s) != hipSuccess ||
+		    hipMemsetAsync(so->rst_seq, 0, 4 * (size_t)in->m, s) != hipSuccess ||
+		    hipMemsetAsync(so->state_after, 0, in->m, s) != hipSuccess)
+			return -EIO;
+	}
+	if (in->nconn == 0) { /* every TCP segment is NOCONN: nothing to group, walk or lay out */
+		if (in->m)
+			hipLaunchKernelGGL(rx_parse_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
+		if (hipMemsetAsync(out->conn_off, 0, sizeof(uint64_t), s) != hipSuccess)
+			return -EIO;
+		return hipGetLastError() == hipSuccess ? 0 : -EIO;
+	}
+	if (hipMemsetAsync(k.run, 0, 8 * (size_t)in->nconn, s) != hipSuccess)
+		return -EIO;
+	const uint32_t *sorted = k.idx[g.passes - 1];
+	if (in->m) {
+		hipLaunchKernelGGL(rx_parse_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
+		for (uint32_t p = 0; p < g.passes; p++) {
+			const RxPass ps = {p ? k.idx[0] : nullptr, k.idx[p], p * kRxDigitBits, g.nb[p], g.kbits[p]};
+			const RxHistIo io = {k.hist, k.tot};
+			const uint32_t total = ps.nb * k.ranges;
+			const uint32_t nchunks = (total + kRxChunk - 1) / kRxChunk;
+			const dim3 grid((k.ranges + kRxWaves - 1) / kRxWaves);
+			hipLaunchKernelGGL(rx_count_kernel, grid, dim3(kRxThreads), 0, s, k, ps);
+			hipLaunchKernelGGL(rx_scan_sum_kernel<RxHistIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, total, k.csum);
+			hipLaunchKernelGGL(rx_scan_top_kernel<RxHistIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, k.csum, nchunks);
+			hipLaunchKernelGGL(rx_scan_apply_kernel<RxHistIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, total,
+			                   k.csum);
+			hipLaunchKernelGGL(rx_scatter_kernel, grid, dim3(kRxThreads), 0, s, k, ps);
+		}
+		hipLaunchKernelGGL(rx_runs_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k, sorted);
+	}
+	RxfParams kf = {k, nullptr, nullptr, nullptr};
+	RxoParams ko = {};
+	const dim3 wgrid((in->nconn + kRxWaves - 1) / kRxWaves);
+	{
+		kf.rep_acks = full->rep_acks;
+		kf.out_ext = (uint4 *)full->out_ext;
+		kf.xcnt = (uint4 *)(ws + g.bytes);
+	}
+	{
+		const struct gcl_tcprxo_in *oi = ooo->in;
+		const struct gcl_tcprxo_out *oo = ooo->out;
+		uint8_t *at = ws + g.bytes + 16 * (size_t)in->nconn;
+
+		ko.f = kf;
+		ko.q_off = oi->q_off;
+		ko.q = (const uint4 *)oi->q;
+		ko.nq = oi->nq;
+		ko.q_out_cap = oi->q_out_cap;
+		ko.oflags = oo->oflags;
+		ko.skip = oo->skip;
+		ko.qin_state = oo->qin_state;
+		ko.qin_skip = oo->qin_skip;
+		ko.qin_len = oo->qin_len;
+		ko.qin_dst_off = (unsigned long long *)oo->qin_dst_off;
+		ko.qout_off = oo->qout_off;
+		ko.qout = (uint4 *)oo->qout;
+		ko.totals = (unsigned long long *)oo->totals;
+		ko.ocnt = (uint4 *)at;
+		at += 16 * (size_t)in->nconn;
+		ko.qmeta = (uint4 *)at;
+		at += 16 * (size_t)in->nconn;
+		ko.qsum = (uint32_t *)at;
+		at += rx_up16(4 * (((size_t)in->nconn + kRxChunk - 1) / kRxChunk));
+		ko.stage = (uint4 *)at;
+		const RxsParams ks = {ko, sts->state, sts->out->ev, sts->out->rst_seq, sts->out->state_after,
+		                      sts->out->state_out};
+		hipLaunchKernelGGL(rxs_walk_kernel, wgrid, dim3(kRxThreads), 0, s, ks, sorted);
+		const RxQoutIo io = {ko.qmeta, ko.qout_off, ko.totals, in->nconn};
+		const uint32_t nchunks = (in->nconn + kRxChunk - 1) / kRxChunk;
+		hipLaunchKernelGGL(rx_scan_sum_kernel<RxQoutIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn, ko.qsum);
+		hipLaunchKernelGGL(rx_scan_top_kernel<RxQoutIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, ko.qsum, nchunks);
+		hipLaunchKernelGGL(rx_scan_apply_kernel<RxQoutIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn,
+		                   ko.qsum);
+	}
+	{
+		const RxConnIo io = {k.conn, k.out_conn, k.conn_off, in->nconn, k.amask};
+		const uint32_t nchunks = (in->nconn + kRxChunk - 1) / kRxChunk;
+		hipLaunchKernelGGL(rx_scan_sum_kernel<RxConnIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn, k.lsum);
+		hipLaunchKernelGGL(rx_scan_top_kernel<RxConnIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, k.lsum, nchunks);
+		hipLaunchKernelGGL(rx_scan_apply_kernel<RxConnIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn,
+		                   k.lsum);
+	}
+	const dim3 cgrid(std::min<uint32_t>((in->nconn + kRxThreads - 1) / kRxThreads, cus * 2));
+	{
+		if (in->m)
+			hipLaunchKernelGGL(rxf_fix_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
+		hipLaunchKernelGGL(rxo_qout_kernel, wgrid, dim3(kRxThreads), 0, s, ko);
+		if (counts)
+			hipLaunchKernelGGL(rxo_counts_kernel, cgrid, dim3(kRxThreads), 0, s, ko);
+	}
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
 extern "C" int gcl_tcp_rx(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprx_in *in,
                           const struct gcl_tcprx_out *out, uint64_t *counts, void *workspace,
                           size_t workspace_bytes, void *hip_stream)
@@ -1532,4 +2038,28 @@ extern "C" int gcl_tcp_rx_ooo(struct gcl_ctx *c, const struct gcl_batch *b, cons
 	const RxOoo o = {in, ooo};
 
 	return rx_run(c, b, &rin, out, &full, &o, counts, workspace, workspace_bytes, hip_stream);
+}
+
+extern "C" int gcl_tcp_rx_states_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, uint32_t nq, size_t *bytes)
+{
+	return gcl_tcp_rx_ooo_workspace(m, nconn, blocks, nq, bytes);
+}
+
+extern "C" int gcl_tcp_rx_states(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprxs_in *in,
+                                 const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext,
+                                 const struct gcl_tcprxo_out *ooo, const struct gcl_tcprxs_out *st,
+                                 uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+	if (!in || in->size != sizeof(*in) || !st)
+		return -EINVAL;
+	const struct gcl_tcprx_in rin = {sizeof(rin), in->align, in->order, in->m, in->sock, in->l4_status,
+	                                 in->conn, in->nconn, in->blocks};
+	const struct gcl_tcprxo_in oin = {sizeof(oin), in->align, in->order, in->m, in->sock, in->l4_status,
+	                                  in->conn, in->nconn, in->blocks, in->rep_acks, in->q_off, in->q, in->nq,
+	                                  in->q_out_cap};
+	const RxFull full = {in->rep_acks, out_ext};
+	const RxOoo o = {&oin, ooo};
+	const RxStates ss = {in->state, st};
+
+	return rxs_run(c, b, &rin, out, &full, &o, &ss, counts, workspace, workspace_bytes, hip_stream);
 }

@@ -159,4 +159,43 @@ GCL_TMR_FN uint32_t gcl_rxack_wnd(uint32_t rcv_wnd, uint32_t rcv_nxt, uint32_t a
 	return rcv_wnd - (after - rcv_nxt);
 }
 
+/*
+ * gcl_tcp_rx_ctl: the one control segment list entry j of a gcl_tcp_rx_states
+ * call asks for, or GCL_RXCTL_NONE.  Every send_rst path of __tcp_rx_conn goes
+ * to done with do_ack false (tcp_in.c:372-376, :452-456, :462-468), so an entry
+ * has at most one; the ACK is asked first, as gcl_tcp_rx_acks asks it.
+ */
+#define GCL_RXCTL_NONE 0xFFu
+GCL_TMR_FN uint32_t gcl_rxctl_kind(uint32_t verdict, uint32_t sflags, uint32_t ev)
+{
+	if (verdict != GCL_TCPRX_FAST)
+		return GCL_RXCTL_NONE;
+	if (sflags & GCL_TCPRX_SF_ACK_NOW)
+		return GCL_CTL_ACK;
+	if (ev & GCL_TCPS_RST)
+		return GCL_CTL_RST;
+	if (ev & GCL_TCPS_RST_ACK)
+		return GCL_CTL_RST_ACK;
+	return GCL_RXCTL_NONE;
+}
+
+/*
+ * struct gcl_txh_desc of tcp_tx_raw_rst (runtime/net/tcp_out.c:98-128: flags
+ * RST, seq = @rst_seq, ack 0) or tcp_tx_raw_rst_ack (:139-170: flags RST|ACK,
+ * seq 0, ack = @rst_seq): off 5, win 0, no payload.
+ */
+GCL_TMR_FN void gcl_ctl_rst_desc(const uint32_t a[4], uint32_t kind, uint32_t rst_seq, uint32_t d[8])
+{
+	const uint32_t fl = kind == GCL_CTL_RST ? 0x04u : 0x14u;
+
+	d[0] = a[0];
+	d[1] = a[1];
+	d[2] = a[2];
+	d[3] = 6u | fl << 8 | 5u << 16;
+	d[4] = kind == GCL_CTL_RST ? rst_seq : 0;
+	d[5] = kind == GCL_CTL_RST ? 0 : rst_seq;
+	d[6] = 0;
+	d[7] = 0;
+}
+
 #endif /* GCL_TCPTMR_H */

@@ -328,6 +328,105 @@ __global__ void __launch_bounds__(kTmrThreads) ctl_emit_kernel(CtlParams k, Src 
 		atomicAdd(k.counts + Src::kNospaceSlot, (unsigned long long)nospace);
 }
 
+/* ---- gcl_tcp_rx_ctl: gcl_tcp_rx_acks' three launches with the RSTs of a gcl_tcp_rx_states call ---- */
+
+struct RxctlParams {
+	RxackParams a;
+	const uint8_t *ev;
+	const uint32_t *rst_seq;
+};
+
+/* list entry j: its kind and connection when it emits a segment; GCL_RXCTL_NONE, @skip set when only the guards keep it from one */
+__device__ __forceinline__ uint32_t rxctl_want(const CtlParams &k, const RxctlParams &p, uint64_t j, uint32_t *conn,
+                                               bool *skip)
+{
+	*conn = 0;
+	*skip = false;
+	const uint32_t kind = gcl_rxctl_kind(p.a.verdict[j], p.a.sflags[j], p.ev[j]);
+	if (kind == GCL_RXCTL_NONE)
+		return kind;
+	const uint64_t i = p.a.order ? p.a.order[j] : j;
+	const uint32_t c = i < p.a.n ? p.a.sock[i] : 0xFFFFFFFFu;
+	if (c >= k.nconn) {
+		*skip = true;
+		return GCL_RXCTL_NONE;
+	}
+	*conn = c;
+	return kind;
+}
+
+__global__ void __launch_bounds__(kTmrThreads) rxctl_decide_kernel(CtlParams k, RxctlParams p)
+{
+	const uint64_t lo = (uint64_t)blockIdx.x * k.per;
+	const uint64_t hi = lo + k.per < k.items ? lo + k.per : k.items;
+	uint32_t segs = 0, skipped = 0; /* wave-uniform */
+
+	for (uint64_t j0 = lo; j0 < hi; j0 += kTmrThreads) { /* uniform: every lane reaches the ballots */
+		const uint64_t j = j0 + threadIdx.x;
+		uint32_t c;
+		bool skip = false;
+		const uint32_t kind = j < hi ? rxctl_want(k, p, j, &c, &skip) : GCL_RXCTL_NONE;
+		segs += (uint32_t)__popcll(__ballot(kind != GCL_RXCTL_NONE));
+		skipped += (uint32_t)__popcll(__ballot(skip));
+	}
+	if (k.counts && (threadIdx.x & 63) == 0 && skipped)
+		atomicAdd(k.counts + GCL_RXACKC_SKIPPED, (unsigned long long)skipped);
+	ctl_store_sum(k, segs);
+}
+
+/* ctl_emit_kernel's positions for one segment a lane at the most; segment at < seg_cap of connection c < nconn */
+__global__ void __launch_bounds__(kTmrThreads) rxctl_emit_kernel(CtlParams k, RxctlParams p)
+{
+	__shared__ uint32_t wt[2][kTmrWaves];
+	const uint64_t lo = (uint64_t)blockIdx.x * k.per;
+	const uint64_t hi = lo + k.per < k.items ? lo + k.per : k.items;
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const uint64_t below = (1ull << lane) - 1;
+	uint64_t carry = lo < hi ? k.bsum[blockIdx.x] : 0; /* the range's base, then the tiles before */
+	uint32_t par = 0;
+
+	for (uint64_t j0 = lo; j0 < hi; j0 += kTmrThreads, par ^= 1) { /* uniform: every lane active */
+		const uint64_t j = j0 + threadIdx.x;
+		uint32_t c = 0;
+		bool skip = false;
+		const uint32_t kind = j < hi ? rxctl_want(k, p, j, &c, &skip) : GCL_RXCTL_NONE;
+		const uint64_t m0 = __ballot(kind != GCL_RXCTL_NONE);
+
+		if (lane == 0)
+			wt[par][wave] = (uint32_t)__popcll(m0);
+		__syncthreads();
+		const uint32_t w0 = wt[par][0], w1 = wt[par][1], w2 = wt[par][2], w3 = wt[par][3];
+		uint64_t at = carry + (uint32_t)__popcll(m0 & below);
+		if (wave > 0)
+			at += w0;
+		if (wave > 1)
+			at += w1;
+		if (wave > 2)
+			at += w2;
+		carry += (uint64_t)w0 + w1 + w2 + w3;
+
+		if (kind != GCL_RXCTL_NONE && c < k.nconn && at < k.seg_cap) {
+			const uint4 ad = k.addr[c];
+			if (kind == GCL_CTL_ACK) {
+				const uint4 c0 = k.conn[3 * (size_t)c], c1 = k.conn[3 * (size_t)c + 1];
+				const uint32_t ack = p.a.after[j];
+				ctl_store(k, at, c, GCL_CTL_ACK, (uint32_t)j, ack, gcl_rxack_wnd(c1.z, c1.y, ack), c0, ad);
+			} else {
+				const uint32_t a[4] = {ad.x, ad.y, ad.z, ad.w};
+				uint32_t d[8];
+
+				gcl_ctl_rst_desc(a, kind, p.rst_seq[j], d);
+				k.desc[2 * at] = make_uint4(d[0], d[1], d[2], d[3]);
+				k.desc[2 * at + 1] = make_uint4(d[4], d[5], d[6], d[7]);
+				k.frame_off[at] = k.frame_base + at * k.frame_stride;
+				k.seg_conn[at] = c;
+				k.seg_kind[at] = (uint8_t)kind;
+				k.seg_src[at] = (uint32_t)j;
+			}
+		}
+	}
+}
+
 static bool tmr_misaligned(const void *p, uintptr_t a)
 {
 	return ((uintptr_t)p & (a - 1)) != 0;
@@ -475,5 +574,52 @@ extern "C" int gcl_tcp_rx_acks(struct gcl_ctx *c, const struct gcl_rxack_in *in,
 	hipLaunchKernelGGL(rxack_decide_kernel, dim3(k.blocks), dim3(kTmrThreads), 0, s, k, p);
 	hipLaunchKernelGGL(ctl_top_kernel, dim3(1), dim3(kTmrThreads), 0, s, k);
 	hipLaunchKernelGGL(ctl_emit_kernel<RxackSrc>, dim3(k.blocks), dim3(kTmrThreads), 0, s, k, src);
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+extern "C" int gcl_tcp_rx_ctl_workspace(uint64_t m, uint32_t blocks, size_t *bytes)
+{
+	return gcl_tcp_rx_acks_workspace(m, blocks, bytes);
+}
+
+extern "C" int gcl_tcp_rx_ctl(struct gcl_ctx *c, const struct gcl_rxctl_in *in, const struct gcl_ctlseg_out *out,
+                              uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+	hipStream_t s = (hipStream_t)hip_stream;
+
+	if (!c || !in || !out || in->size != sizeof(*in) || in->m > (1ull << 31) ||
+	    ctl_refused(in->nconn, in->blocks, in->seg_cap, in->frame_stride, in->m, out, counts, workspace,
+	                workspace_bytes))
+		return -EINVAL;
+	if (in->m && (!in->sock || !in->verdict || !in->sflags || !in->rcv_nxt_after || !in->ev || !in->rst_seq))
+		return -EINVAL;
+	if (in->m && in->nconn && (!in->conn || !in->addr))
+		return -EINVAL;
+	if (tmr_misaligned(in->order, 4) || tmr_misaligned(in->sock, 4) || tmr_misaligned(in->rcv_nxt_after, 4) ||
+	    tmr_misaligned(in->conn, 16) || tmr_misaligned(in->addr, 16) || tmr_misaligned(in->rst_seq, 4))
+		return -EINVAL;
+	if (hipSetDevice(c->device) != hipSuccess)
+		return -EIO;
+	c->last_stream = s;
+
+	if (in->m == 0)
+		return hipMemsetAsync(out->totals, 0, 2 * sizeof(uint64_t), s) == hipSuccess ? 0 : -EIO;
+
+	CtlParams k;
+	ctl_fill(&k, c, out, counts, workspace, in->m, in->blocks);
+	k.conn = (const uint4 *)in->conn;
+	k.addr = (const uint4 *)in->addr;
+	k.nconn = in->nconn;
+	k.seg_cap = in->seg_cap;
+	k.frame_base = in->frame_base;
+	k.frame_stride = in->frame_stride;
+	k.cnt_wanted = GCL_RXACKC_WANTED;
+	k.cnt_written = GCL_RXACKC_WRITTEN;
+	const RxctlParams p = {{in->order, in->sock, in->verdict, in->sflags, in->rcv_nxt_after, in->n}, in->ev,
+	                       in->rst_seq};
+
+	hipLaunchKernelGGL(rxctl_decide_kernel, dim3(k.blocks), dim3(kTmrThreads), 0, s, k, p);
+	hipLaunchKernelGGL(ctl_top_kernel, dim3(1), dim3(kTmrThreads), 0, s, k);
+	hipLaunchKernelGGL(rxctl_emit_kernel, dim3(k.blocks), dim3(kTmrThreads), 0, s, k, p);
 	return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }

@@ -134,6 +134,14 @@ OOOQ_UNTOUCHED, OOOQ_KEPT, OOOQ_FREED, OOOQ_DRAINED = 0, 1, 2, 3
 (TCPRXOC_OOO, TCPRXOC_QUEUED, TCPRXOC_DRAINED, TCPRXOC_FREED, TCPRXOC_HEADCLIP, TCPRXOC_HELD,
  TCPRXOC_NR) = 13, 14, 15, 16, 17, 18, 19
 TCP_OOO_ENT_DTYPE = np.dtype([("seq", "<u4"), ("end", "<u4"), ("ref", "<u4"), ("flags", "<u2"), ("src", "<u2")])
+# gcl_tcp_rx_states: enum tcp state, ev[j], the xflags it adds and the counters behind gcl_tcp_rx_ooo's nineteen
+(TCP_STATE_SYN_SENT, TCP_STATE_SYN_RECEIVED, TCP_STATE_ESTABLISHED, TCP_STATE_FIN_WAIT1, TCP_STATE_FIN_WAIT2,
+ TCP_STATE_CLOSE_WAIT, TCP_STATE_CLOSING, TCP_STATE_LAST_ACK, TCP_STATE_TIME_WAIT, TCP_STATE_CLOSED) = range(10)
+TCPS_NOSTATE = 0xFF
+TCPS_RST, TCPS_RST_ACK, TCPS_FAIL, TCPS_STATE, TCPS_FIN, TCPS_PUT = 1, 2, 4, 8, 0x10, 0x20
+TCPX_FAILED, TCPX_PUT, TCPX_TIMEWAIT, TCPX_OPENED = 0x08, 0x10, 0x20, 0x40
+CTL_RST, CTL_RST_ACK = 2, 3      # seg_kind of gcl_tcp_rx_ctl beside CTL_ACK and CTL_PROBE
+TCPRXSC_RSTS, TCPRXSC_FAILS, TCPRXSC_FINS, TCPRXSC_STATE_CHANGES, TCPRXSC_NR = 19, 20, 21, 22, 23
 # gcl_tcp_tick / gcl_tcp_rx_acks: the timer flags, the action bits (bits 0..6 are also the first
 # counter slots), the segment kinds, the counters, the caps, the TCP states the sweep tests,
 # struct gcl_tcp_tmr, struct gcl_tcp_tmr_out and struct gcl_tcp_addr
@@ -436,6 +444,18 @@ class GclTcprxoOut(ctypes.Structure):
     _fields_ = [(f, ctypes.c_void_p) for f, _, _ in TCPRXO_OUT_FIELDS]
 
 
+class GclTcprxsIn(ctypes.Structure):
+    _fields_ = GclTcprxoIn._fields_ + [("state", ctypes.c_void_p)]
+
+
+# struct gcl_tcprxs_out: (field, bytes per element, which count it is sized by)
+TCPRXS_OUT_FIELDS = (("ev", 1, "m"), ("rst_seq", 4, "m"), ("state_after", 1, "m"), ("state_out", 1, "nconn"))
+
+
+class GclTcprxsOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f, _, _ in TCPRXS_OUT_FIELDS]
+
+
 TCPRX_ENTRY_FIELDS = ("verdict", "sflags", "rcv_nxt_after", "copy_len", "dst_off")
 TCPRX_OUT_FIELDS = TCPRX_ENTRY_FIELDS + ("out_conn", "conn_off")
 
@@ -472,6 +492,10 @@ class GclRxackIn(ctypes.Structure):
                 ("frame_stride", ctypes.c_uint32), ("seg_cap", ctypes.c_uint64), ("frame_base", ctypes.c_uint64)]
 
 
+class GclRxctlIn(ctypes.Structure):
+    _fields_ = GclRxackIn._fields_ + [("ev", ctypes.c_void_p), ("rst_seq", ctypes.c_void_p)]
+
+
 class GclTxqIn(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("now", ctypes.c_uint64),
                 ("qoff", ctypes.c_void_p), ("ent", ctypes.c_void_p), ("cold", ctypes.c_void_p),
@@ -496,6 +520,8 @@ assert TCP_ADDR_DTYPE.itemsize == 16
 assert ctypes.sizeof(GclTcprxIn) == 56 and ctypes.sizeof(GclTcprxOut) == 56
 assert ctypes.sizeof(GclTcprxfIn) == 64 and TCP_CONN_EXT_DTYPE.itemsize == 16
 assert ctypes.sizeof(GclTcprxoIn) == 88 and ctypes.sizeof(GclTcprxoOut) == 72 and TCP_OOO_ENT_DTYPE.itemsize == 16
+assert ctypes.sizeof(GclRxctlIn) == 120
+assert ctypes.sizeof(GclTcprxsIn) == 96 and ctypes.sizeof(GclTcprxsOut) == 32
 assert TCP_CONN_DTYPE.itemsize == 48 and TCP_CONN_OUT_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclSegIn) == 64 and ctypes.sizeof(GclSegOut) == 104 and SEG_SEND_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclTxhIn) == 88 and ctypes.sizeof(GclTxhNet) == 20 and TXH_DESC_DTYPE.itemsize == 32
@@ -613,10 +639,21 @@ def _load():
                                  ctypes.c_size_t, vp]),
         "gcl_tcp_rx_ooo_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxoIn),
                                       ctypes.POINTER(GclTcprxOut), vp, ctypes.POINTER(GclTcprxoOut), vp]),
+        "gcl_tcp_rx_states_workspace": (i32, [u64, u32, u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_rx_states": (i32, [vp, ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxsIn),
+                                    ctypes.POINTER(GclTcprxOut), vp, ctypes.POINTER(GclTcprxoOut),
+                                    ctypes.POINTER(GclTcprxsOut), vp, vp, ctypes.c_size_t, vp]),
+        "gcl_tcp_rx_states_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcprxsIn),
+                                         ctypes.POINTER(GclTcprxOut), vp, ctypes.POINTER(GclTcprxoOut),
+                                         ctypes.POINTER(GclTcprxsOut), vp]),
         "gcl_tcp_tick_workspace": (i32, [u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
         "gcl_tcp_tick": (i32, [vp, ctypes.POINTER(GclTickIn), ctypes.POINTER(GclTickOut), vp, vp,
                                ctypes.c_size_t, vp]),
         "gcl_tcp_tick_host": (i32, [ctypes.POINTER(GclTickIn), ctypes.POINTER(GclTickOut), vp]),
+        "gcl_tcp_rx_ctl_workspace": (i32, [u64, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_rx_ctl": (i32, [vp, ctypes.POINTER(GclRxctlIn), ctypes.POINTER(GclCtlsegOut), vp, vp,
+                                 ctypes.c_size_t, vp]),
+        "gcl_tcp_rx_ctl_host": (i32, [ctypes.POINTER(GclRxctlIn), ctypes.POINTER(GclCtlsegOut), vp]),
         "gcl_tcp_rx_acks_workspace": (i32, [u64, u32, ctypes.POINTER(ctypes.c_size_t)]),
         "gcl_tcp_rx_acks": (i32, [vp, ctypes.POINTER(GclRxackIn), ctypes.POINTER(GclCtlsegOut), vp, vp,
                                   ctypes.c_size_t, vp]),
@@ -1284,6 +1321,68 @@ def tcp_rx_ooo_workspace(m, nconn, blocks=0, nq=0):
     return need.value
 
 
+def _tcprxs_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status, conn, nconn,
+                    align, blocks, out, counts, rep_acks, q_off, q, nq, q_out_cap, state):
+    """The five structs of gcl_tcp_rx_states / gcl_tcp_rx_states_host, sizes
+    checked; @out maps TCPRX_OUT_FIELDS, "out_ext", TCPRXO_OUT_FIELDS and
+    TCPRXS_OUT_FIELDS to buffers."""
+    if counts is not None and _nbytes(counts) < 8 * TCPRXSC_NR:
+        raise ValueError("counts buffer too small")
+    if state is not None and _nbytes(state) < nconn:
+        raise ValueError("state too small")
+    size = {"m": m, "nconn": nconn}
+    for f, w, by in TCPRXS_OUT_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < w * size[by]:
+            raise ValueError(f"{f} too small")
+    b, oin, rout, oout = _tcprxo_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status,
+                                         conn, nconn, align, blocks, out, None, rep_acks, q_off, q, nq, q_out_cap)
+    sin = GclTcprxsIn(size=ctypes.sizeof(GclTcprxsIn), align=align, order=oin.order, m=m, sock=oin.sock,
+                      l4_status=oin.l4_status, conn=oin.conn, nconn=nconn, blocks=blocks, rep_acks=oin.rep_acks,
+                      q_off=oin.q_off, q=oin.q, nq=nq, q_out_cap=q_out_cap, state=_ptr(state))
+    sout = GclTcprxsOut(**{f: _ptr(out[f]) for f, _, _ in TCPRXS_OUT_FIELDS})
+    return b, sin, rout, oout, sout
+
+
+def tcp_rx_states_host(frames, pkt_len, sock, conn, stride=0, offs=None, n=None, frames_len=None, order=None,
+                       m=None, l4_status=None, nconn=None, align=0, blocks=0, rep_acks=None, q_off=None, q=None,
+                       nq=None, q_out_cap=0, state=None, out=None, counts=None):
+    """gcl_tcp_rx_states_host: the rule of Classifier.tcp_rx_states on the CPU
+    over numpy arrays: tcp_rx_ooo_host's arguments and @state (u8[nconn] of
+    TCP_STATE_*, None: the connections' flags decide); in @out also the fields
+    of TCPRXS_OUT_FIELDS.  @counts is a u64[TCPRXSC_NR], accumulated.  Returns
+    the dict."""
+    n = len(pkt_len) if n is None else n
+    m = _pay_m(n, m, order)
+    nconn = len(conn) if nconn is None else nconn
+    nq = (0 if q is None else len(q)) if nq is None else nq
+    out = dict(out or {})
+    size = _tcprxo_sizes(m, nconn, nq, q_out_cap)
+    size["nconn"] = nconn
+    for f, dt, k in (("verdict", np.uint8, m), ("sflags", np.uint8, m), ("rcv_nxt_after", np.uint32, m),
+                     ("copy_len", np.uint16, m), ("dst_off", np.uint64, m),
+                     ("out_conn", TCP_CONN_OUT_DTYPE, nconn), ("conn_off", np.uint64, nconn + 1),
+                     ("out_ext", TCP_CONN_EXT_DTYPE, nconn)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    for f, w, by in TCPRXO_OUT_FIELDS + TCPRXS_OUT_FIELDS:
+        if f not in out:
+            out[f] = np.zeros(max(size[by], 1), dtype=TCP_OOO_ENT_DTYPE if f == "qout" else f"<u{w}")
+    b, sin, rout, oout, sout = _tcprxs_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock,
+                                               l4_status, conn, nconn, align, blocks, out, counts, rep_acks, q_off,
+                                               q, nq, q_out_cap, state)
+    _check(lib.gcl_tcp_rx_states_host(ctypes.byref(b), ctypes.byref(sin), ctypes.byref(rout), _ptr(out["out_ext"]),
+                                      ctypes.byref(oout), ctypes.byref(sout), _ptr(counts)),
+           "gcl_tcp_rx_states_host")
+    return out
+
+
+def tcp_rx_states_workspace(m, nconn, blocks=0, nq=0):
+    """gcl_tcp_rx_states_workspace: bytes of device scratch a call over @m entries, @nconn connections and @nq input queue entries takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_rx_states_workspace(m, nconn, blocks, nq, ctypes.byref(need)), "gcl_tcp_rx_states_workspace")
+    return need.value
+
+
 CTLSEG_OUT_WIDTH = {"desc": 32, "frame_off": 8, "seg_conn": 4, "seg_kind": 1, "seg_src": 4}
 
 
@@ -1374,6 +1473,43 @@ def tcp_rx_acks_host(verdict, sflags, rcv_nxt_after, sock, conn, addr, seg_cap, 
                                frame_base, frame_stride, blocks, out, counts)
     _check(lib.gcl_tcp_rx_acks_host(ctypes.byref(rin), ctypes.byref(rout), _ptr(counts)), "gcl_tcp_rx_acks_host")
     return out
+
+
+def _rxctl_structs(verdict, sflags, rcv_nxt_after, ev, rst_seq, sock, conn, addr, m, n, nconn, order, seg_cap,
+                   frame_base, frame_stride, blocks, out, counts):
+    """The two structs of gcl_tcp_rx_ctl / gcl_tcp_rx_ctl_host, sizes checked"""
+    for arr, w in ((ev, 1), (rst_seq, 4)):
+        if arr is not None and _nbytes(arr) < w * m:
+            raise ValueError("per-entry array too small")
+    rin, rout = _rxack_structs(verdict, sflags, rcv_nxt_after, sock, conn, addr, m, n, nconn, order, seg_cap,
+                               frame_base, frame_stride, blocks, out, counts)
+    cin = GclRxctlIn(**{f: getattr(rin, f) for f, _ in GclRxackIn._fields_})
+    cin.size, cin.ev, cin.rst_seq = ctypes.sizeof(GclRxctlIn), _ptr(ev), _ptr(rst_seq)
+    return cin, rout
+
+
+def tcp_rx_ctl_host(verdict, sflags, rcv_nxt_after, ev, rst_seq, sock, conn, addr, seg_cap, frame_stride=64,
+                    frame_base=0, order=None, m=None, n=None, nconn=None, blocks=0, out=None, counts=None):
+    """gcl_tcp_rx_ctl_host: the rule of Classifier.tcp_rx_ctl on the CPU over
+    numpy arrays: tcp_rx_acks_host's arguments and @ev and @rst_seq as
+    tcp_rx_states_host wrote them.  Returns the dict; seg_kind also holds
+    CTL_RST and CTL_RST_ACK."""
+    m = len(verdict) if m is None else m
+    n = len(sock) if n is None else n
+    nconn = len(conn) if nconn is None else nconn
+    out = dict(out or {})
+    _ctlseg_host_arrays(out, seg_cap)
+    cin, rout = _rxctl_structs(verdict, sflags, rcv_nxt_after, ev, rst_seq, sock, conn, addr, m, n, nconn, order,
+                               seg_cap, frame_base, frame_stride, blocks, out, counts)
+    _check(lib.gcl_tcp_rx_ctl_host(ctypes.byref(cin), ctypes.byref(rout), _ptr(counts)), "gcl_tcp_rx_ctl_host")
+    return out
+
+
+def tcp_rx_ctl_workspace(m, blocks=0):
+    """gcl_tcp_rx_ctl_workspace: bytes of device scratch a call over @m list entries takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_rx_ctl_workspace(m, blocks, ctypes.byref(need)), "gcl_tcp_rx_ctl_workspace")
+    return need.value
 
 
 def tcp_tick_workspace(nconn, blocks=0):
@@ -2113,6 +2249,48 @@ class Classifier:
                                   stream), "gcl_tcp_rx_ooo")
         return out
 
+    def tcp_rx_states(self, frames, n, pkt_len, sock, conn, nconn, stride=0, offs=None, frames_len=None,
+                      order=None, m=None, l4_status=None, align=0, blocks=0, rep_acks=None, q_off=None, q=None,
+                      nq=0, q_out_cap=0, state=None, out=None, counts=None, workspace=None, stream=None):
+        """gcl_tcp_rx_states: tcp_rx_conn with all of __tcp_rx_conn (FIN, RST,
+        SYN, URG and every state but SYN_SENT) for one runtime's list on the
+        GPU, asynchronous.  The arguments are tcp_rx_ooo's and @state, a device
+        uint8[nconn] of TCP_STATE_* (None: the connections' flags decide).
+        @out also holds the fields of TCPRXS_OUT_FIELDS (ev, state_after and
+        state_out uint8, rst_seq int32) and @counts is a device
+        u64[TCPRXSC_NR], accumulated.  Returns the dict: ev and rst_seq say
+        which RST to send, out_ext's xflags what the runtime still owes."""
+        import torch
+        m = _pay_m(n, m, order)
+        dev = frames.device if hasattr(frames, "device") else None
+        out = dict(out or {})
+        mm = max(m, 1)
+        size = _tcprxo_sizes(m, nconn, nq, q_out_cap)
+        size["nconn"] = nconn
+        for f, dt, shape in (("verdict", torch.uint8, (mm,)), ("sflags", torch.uint8, (mm,)),
+                             ("rcv_nxt_after", torch.int32, (mm,)), ("copy_len", torch.int16, (mm,)),
+                             ("dst_off", torch.int64, (mm,)), ("out_conn", torch.uint8, (max(nconn, 1), 48)),
+                             ("conn_off", torch.int64, (nconn + 1,)),
+                             ("out_ext", torch.uint8, (max(nconn, 1), 16))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        for f, w, by in TCPRXO_OUT_FIELDS + TCPRXS_OUT_FIELDS:
+            if f not in out:
+                out[f] = torch.empty((max(size[by], 1), w), dtype=torch.uint8, device=dev)
+        b, sin, rout, oout, sout = _tcprxs_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock,
+                                                   l4_status, conn, nconn, align, blocks, out, counts, rep_acks,
+                                                   q_off, q, nq, q_out_cap, state)
+        ws = workspace
+        if ws is None:
+            need = tcp_rx_states_workspace(m, nconn, blocks, nq)
+            ws = getattr(self, "_tcprx_ws", None)
+            if ws is None or ws.numel() < need or ws.device != out["conn_off"].device:
+                ws = self._tcprx_ws = torch.empty(need, dtype=torch.uint8, device=out["conn_off"].device)
+        _check(lib.gcl_tcp_rx_states(self._ctx, ctypes.byref(b), ctypes.byref(sin), ctypes.byref(rout),
+                                     _ptr(out["out_ext"]), ctypes.byref(oout), ctypes.byref(sout), _ptr(counts),
+                                     _ptr(ws), _nbytes(ws), stream), "gcl_tcp_rx_states")
+        return out
+
     def _ctlseg_device_arrays(self, out, seg_cap, dev):
         import torch
         cc = max(seg_cap, 1)
@@ -2178,6 +2356,25 @@ class Classifier:
                                                                    out["totals"].device)
         _check(lib.gcl_tcp_rx_acks(self._ctx, ctypes.byref(rin), ctypes.byref(rout), _ptr(counts), _ptr(ws),
                                    _nbytes(ws), stream), "gcl_tcp_rx_acks")
+        return out
+
+    def tcp_rx_ctl(self, verdict, sflags, rcv_nxt_after, ev, rst_seq, m, sock, n, conn, addr, nconn, seg_cap,
+                   order=None, frame_stride=64, frame_base=0, blocks=0, out=None, counts=None, workspace=None,
+                   stream=None):
+        """gcl_tcp_rx_ctl: the control segments of one tcp_rx_states call on
+        the GPU, asynchronous: tcp_rx_acks' ACKs and, in list order among
+        them, the RST and RST|ACK segments that @ev and @rst_seq name.  The
+        other arguments and the returned dict are tcp_rx_acks'; seg_kind also
+        holds CTL_RST and CTL_RST_ACK."""
+        dev = verdict.device if hasattr(verdict, "device") else None
+        out = dict(out or {})
+        self._ctlseg_device_arrays(out, seg_cap, dev)
+        cin, rout = _rxctl_structs(verdict, sflags, rcv_nxt_after, ev, rst_seq, sock, conn, addr, m, n, nconn,
+                                   order, seg_cap, frame_base, frame_stride, blocks, out, counts)
+        ws = workspace if workspace is not None else self._tick_ws(tcp_rx_ctl_workspace(m, blocks),
+                                                                   out["totals"].device)
+        _check(lib.gcl_tcp_rx_ctl(self._ctx, ctypes.byref(cin), ctypes.byref(rout), _ptr(counts), _ptr(ws),
+                                  _nbytes(ws), stream), "gcl_tcp_rx_ctl")
         return out
 
     def tcp_txq(self, now, qoff, ent, cold, nent, conn, addr, nconn, seg_cap, want=None, frame_stride=64,

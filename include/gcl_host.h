@@ -275,6 +275,21 @@ int gcl_tcp_rx_ooo_host(const struct gcl_batch *b, const struct gcl_tcprxo_in *i
                         const struct gcl_tcprxo_out *ooo, uint64_t *counts);
 
 /*
+ * gcl_tcp_rx_states_host - the rule of gcl_tcp_rx_states (gclassify.h) on the
+ * CPU over host pointers: gcl_tcp_rx_ooo_host's threading and walk with every
+ * connection's live state beside its queue, composed of the pieces of
+ * csrc/gcl_tcprxs.h that the kernel composes.  It allocates 4 (m + 2 nconn)
+ * bytes for the threading and frees them before it returns; no workspace.
+ * @counts is a host u64[GCL_TCPRXSC_NR], ACCUMULATED, may be NULL.  The same
+ * outputs byte for byte, the same counts and the same guarantee.  0, -EINVAL
+ * for what gcl_tcp_rx_states refuses (the ctx and the workspace apart), or
+ * -ENOMEM.
+ */
+int gcl_tcp_rx_states_host(const struct gcl_batch *b, const struct gcl_tcprxs_in *in,
+                           const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext,
+                           const struct gcl_tcprxo_out *ooo, const struct gcl_tcprxs_out *st, uint64_t *counts);
+
+/*
  * gcl_tcp_tick_host, gcl_tcp_rx_acks_host - the rules of gcl_tcp_tick and
  * gcl_tcp_rx_acks (gclassify.h) on the CPU over host pointers, for the sweeps
  * and lists the GPU did not see: tcp_worker's walk with tcp_handle_timeouts and
@@ -289,6 +304,15 @@ int gcl_tcp_rx_ooo_host(const struct gcl_batch *b, const struct gcl_tcprxo_in *i
  * calls refuse (the ctx and the workspace apart).
  */
 int gcl_tcp_tick_host(const struct gcl_tick_in *in, const struct gcl_tick_out *out, uint64_t *counts);
+/*
+ * gcl_tcp_rx_ctl_host - the rule of gcl_tcp_rx_ctl (gclassify.h) on the CPU
+ * over host pointers: one walk over the list with gcl_rxctl_kind and
+ * gcl_ctl_rst_desc of csrc/gcl_tcptmr.h.  @counts is a host u64[GCL_TICKC_NR],
+ * ACCUMULATED (GCL_RXACKC_* slots), may be NULL.  The same outputs byte for
+ * byte.  0, or -EINVAL for what gcl_tcp_rx_ctl refuses (the ctx and the
+ * workspace apart).
+ */
+int gcl_tcp_rx_ctl_host(const struct gcl_rxctl_in *in, const struct gcl_ctlseg_out *out, uint64_t *counts);
 int gcl_tcp_rx_acks_host(const struct gcl_rxack_in *in, const struct gcl_ctlseg_out *out, uint64_t *counts);
 
 /*

@@ -2116,6 +2116,158 @@ int gcl_tcp_rx_ooo(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct 
                    void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /*
+ * TCP receive in every state: gcl_tcp_rx_states stands where gcl_tcp_rx_ooo
+ * stands, takes the same inputs and one more, the connections' states, and
+ * finishes __tcp_rx_conn (runtime/net/tcp_in.c:352-611): FIN, RST, SYN and URG
+ * segments no longer stop a connection, and a connection in SYN_RECEIVED,
+ * FIN_WAIT1, FIN_WAIT2, CLOSE_WAIT, CLOSING, LAST_ACK, TIME_WAIT or CLOSED is
+ * walked as one in ESTABLISHED is.
+ *
+ *   gcl_l4_payload -> gcl_tcp_rx_states -> gcl_copy_batch (src_off + skip)
+ *                  -> gcl_tcp_rx_ctl (the ACKs of ACK_NOW and the RSTs of ev / rst_seq)
+ *                  -> gcl_tcp_txq
+ *
+ * @in is gcl_tcprxo_in's fields with its own size and state: an optional
+ * device u8[nconn], enum tcp state (runtime/net/tcp.h:41-52, GCL_TCP_STATE_*).
+ * With state == NULL a connection is in ESTABLISHED exactly when its flags
+ * have GCL_TCPC_ELIGIBLE or GCL_TCPC_ESTABLISHED and is otherwise not taken:
+ * gcl_tcp_rx_ooo's meaning.  With state given, state[c] decides and the two
+ * flag bits are ignored.  A connection is TAKEN when its state is 1..9 and its
+ * input queue has at most GCL_TCPOOO_CAP entries; FIN entries in the queue no
+ * longer bar it.  SYN_SENT (0) and values above 9 are not taken.
+ *
+ * For one segment of a taken connection that has not stopped, in list order,
+ * after the lines NA, NOCONN and DROP of gcl_tcp_rx; `state` is the LIVE one:
+ *  1. The fast path, exactly when gcl_tcp_rx's rule says FAST, the live state
+ *     is ESTABLISHED and the live queue is empty.  A connection that becomes
+ *     ESTABLISHED in mid-list may take it for its later segments.
+ *  2. Otherwise __tcp_rx_conn (sflags RULE2), with len counting a FIN as one
+ *     (:369-370) in the acceptability test, in the duplicate-ACK test len == 0
+ *     and in seg_end (:552):
+ *     state CLOSED (:372-376): RST|ACK with seq 0 and ack seq + len unless the
+ *       segment carries RST; done.
+ *     not acceptable: do_ack unless the segment carries RST (:439); done.
+ *     RST (:444): FAIL; done.
+ *     SYN (:452): RST with seq = ack when the segment carries ACK, else RST|ACK
+ *       with ack = seq + len; FAIL; done.
+ *     no ACK flag: done.
+ *     SYN_RECEIVED (:462-473): not snd_una <= ack <= snd_nxt: RST with seq =
+ *       ack, done; else snd_wnd, snd_wl1, snd_wl2 = win, seq, ack (WND) and the
+ *       state is ESTABLISHED (GCL_TCPX_OPENED: tcp_conn_set_state's
+ *       waitq_release of tx_wq and POLLOUT, tcp.c:254-258).
+ *     gcl_tcp_rx_full's ACK, window, TXWAKE and duplicate-ACK lines.
+ *     snd_una == snd_nxt (:530-542): FIN_WAIT1 -> FIN_WAIT2; CLOSING ->
+ *       TIME_WAIT (GCL_TCPX_TIMEWAIT: time_wait_ts = microtime()); LAST_ACK ->
+ *       CLOSED, PUT (tcp_conn_put), done.
+ *     len > 0 and the state is ESTABLISHED, FIN_WAIT1 or FIN_WAIT2: the text
+ *       step of gcl_tcp_rx_ooo; fin is set by an in-order segment that carries
+ *       FIN (:114) and by every drained entry that does (:161), and the drain
+ *       goes on behind such an entry.  In the other states acceptable text is
+ *       dropped and the delayed-ACK lines do not run.
+ *     fin (:578-590): ESTABLISHED -> CLOSE_WAIT; FIN_WAIT1 -> CLOSING;
+ *       FIN_WAIT2 -> TIME_WAIT with do_ack and GCL_TCPX_TIMEWAIT.
+ *     done as in gcl_tcp_rx_full.  URG is not looked at (step 6 is skipped).
+ *  3. A segment with FAIL or PUT is handled and is the last one of its
+ *     connection the call takes: the next one STOPS it (verdict SLOW,
+ *     first_slow).  FAIL leaves the state as it was: tcp_conn_fail is the
+ *     runtime's.  A connection that ENTERS in CLOSED is walked to the end.
+ *     The stop at the 65th insert is gcl_tcp_rx_ooo's, with every word of the
+ *     connection, its state among them, as before the segment.
+ *
+ * Kept as the reference has them.  A FIN's octet is part of seg_end, so
+ * tcp_rx_append_text's tail clip (:83-87) trims the mbuf by a length that
+ * counts it: FIN + 6 bytes into rcv_wnd = 3 links 2 bytes while rcv_nxt moves
+ * by 3.  copy_len[j] (qin_len[i]) is the mbuf length the reference leaves:
+ * the text length - the head pull - the trim, not below 0; an input queue
+ * entry with FIN holds end - seq - 1 bytes of text.  rcv_nxt, rcv_wnd and the
+ * layout stay in sequence space: conn_off[c + 1] - conn_off[c] spans
+ * out_conn[c].rcv_nxt - conn[c].rcv_nxt and dst_off = conn_off[c] + (clipped
+ * seq - conn[c].rcv_nxt), so an accepted FIN leaves one byte of the region
+ * unwritten (THE FIN GAP), and a tail-clipped FIN segment a second one, the
+ * lost tail byte.  After a FIN the state leaves the text states, so only
+ * entries drained behind a FIN entry in the same tcp_rx_text call land behind
+ * that gap.  fin is set even where the clip removed the FIN's own octet.
+ *
+ * Outputs: @out, @out_ext and @ooo are gcl_tcp_rx_ooo's; out_ext.xflags may
+ * also hold GCL_TCPX_FAILED, _PUT, _TIMEWAIT and _OPENED.  @st adds per list
+ * entry ev[j] (GCL_TCPS_*), rst_seq[j] (the seq of a RST, the ack of a
+ * RST|ACK, else 0) and state_after[j], all 0 for an entry that was not
+ * handled; and per connection state_out[c]: the live state after the list,
+ * for a connection that was not taken state[c] as given, or GCL_TCPS_NOSTATE
+ * without a state array.  An entry has at most one of RST and RST_ACK, and
+ * never with ACK_NOW.  @counts is a device u64[GCL_TCPRXSC_NR], ACCUMULATED,
+ * may be NULL: the nineteen of gcl_tcp_rx_ooo, then RSTS (either kind), FAILS,
+ * FINS and STATE_CHANGES (entries with GCL_TCPS_STATE).
+ *
+ * Guarantee: gcl_tcp_rx_ooo's, with state[0, nconn) among the reads and ev,
+ * rst_seq, state_after (m elements) and state_out[0, nconn) among the writes.
+ *
+ * What stays with the runtime: SYN_SENT, which needs iss, winmax and the
+ * options and answers with tcp_tx_ctl(SYN|ACK); tcp_rx_listener and
+ * tcp_rx_closed, the segments with no connection; tcp_timer_update;
+ * tcp_conn_fail's frees and wake-ups and its state CLOSED (FAIL), tcp_conn_put
+ * (PUT), time_wait_ts (TIMEWAIT), the wake of OPENED; and what gcl_tcp_rx_ooo
+ * leaves.  The RSTs are gcl_tcp_rx_ctl's.
+ *
+ * gcl_tcp_rx_states_workspace, gcl_tcp_rx_states - as gcl_tcp_rx_ooo's, the
+ *   same bytes: asynchronous, launches ordered by the stream alone, no block
+ *   waits for another, atomics only add to counts, no allocation, no host
+ *   synchronisation.  -EINVAL for what gcl_tcp_rx_ooo refuses; a NULL st; with
+ *   m > 0 a NULL ev, rst_seq or state_after, or a rst_seq not 4-B aligned; with
+ *   nconn > 0 a NULL state_out.
+ */
+/* enum tcp state: ESTABLISHED 2, TIME_WAIT 8 and CLOSED 9 are defined with gcl_tcp_tmr below */
+#define GCL_TCP_STATE_SYN_SENT     0
+#define GCL_TCP_STATE_SYN_RECEIVED 1
+#define GCL_TCP_STATE_FIN_WAIT1    3
+#define GCL_TCP_STATE_FIN_WAIT2    4
+#define GCL_TCP_STATE_CLOSE_WAIT   5
+#define GCL_TCP_STATE_CLOSING      6
+#define GCL_TCP_STATE_LAST_ACK     7
+#define GCL_TCPS_NOSTATE 0xFF        /* state_out[c] of a connection that is not taken when state == NULL */
+/* ev[j] */
+#define GCL_TCPS_RST     0x01        /* tcp_tx_raw_rst(seq = rst_seq[j]) */
+#define GCL_TCPS_RST_ACK 0x02        /* tcp_tx_raw_rst_ack(seq = 0, ack = rst_seq[j]) */
+#define GCL_TCPS_FAIL    0x04        /* tcp_conn_fail(c, ECONNRESET) */
+#define GCL_TCPS_STATE   0x08        /* tcp_conn_set_state ran: state_after[j] differs from the state before */
+#define GCL_TCPS_FIN     0x10        /* step 8 ran: a FIN was consumed */
+#define GCL_TCPS_PUT     0x20        /* LAST_ACK -> CLOSED: tcp_conn_put, :540 */
+/* gcl_tcp_conn_ext.xflags */
+#define GCL_TCPX_FAILED   0x08       /* some segment had FAIL */
+#define GCL_TCPX_PUT      0x10       /* some segment had PUT */
+#define GCL_TCPX_TIMEWAIT 0x20       /* set time_wait_ts = microtime(), :535 and :587 */
+#define GCL_TCPX_OPENED   0x40       /* SYN_RECEIVED -> ESTABLISHED: waitq_release(tx_wq) + POLLOUT */
+enum { GCL_TCPRXSC_RSTS = 19, GCL_TCPRXSC_FAILS, GCL_TCPRXSC_FINS, GCL_TCPRXSC_STATE_CHANGES,
+       GCL_TCPRXSC_NR = 23 };
+struct gcl_tcprxs_in {
+	uint32_t size, align;            /* sizeof(struct gcl_tcprxs_in) */
+	const uint32_t *order;
+	uint64_t m;
+	const uint32_t *sock;
+	const uint8_t  *l4_status;
+	const struct gcl_tcp_conn *conn;
+	uint32_t nconn;
+	uint32_t blocks;
+	const uint8_t  *rep_acks;
+	const uint32_t *q_off;
+	const struct gcl_tcp_ooo_ent *q;
+	uint32_t nq;
+	uint32_t q_out_cap;
+	const uint8_t  *state;           /* optional u8[nconn]: enum tcp state; NULL: the flags decide */
+};
+struct gcl_tcprxs_out {              /* device, aligned to their element */
+	uint8_t  *ev;                    /* [m] */
+	uint32_t *rst_seq;               /* [m] */
+	uint8_t  *state_after;           /* [m] */
+	uint8_t  *state_out;             /* [nconn] */
+};
+int gcl_tcp_rx_states_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, uint32_t nq, size_t *bytes);
+int gcl_tcp_rx_states(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct gcl_tcprxs_in *in,
+                      const struct gcl_tcprx_out *out, struct gcl_tcp_conn_ext *out_ext,
+                      const struct gcl_tcprxo_out *ooo, const struct gcl_tcprxs_out *st, uint64_t *counts,
+                      void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/*
  * TCP control segments: the timer sweep, and the ACKs of a gcl_tcp_rx call.
  * Both chains end where TCP asks for a segment that carries no data.  In the
  * reference that is per-connection work on a core: tcp_worker
@@ -2321,6 +2473,53 @@ int gcl_tcp_tick(struct gcl_ctx *ctx, const struct gcl_tick_in *in, const struct
 int gcl_tcp_rx_acks_workspace(uint64_t m, uint32_t blocks, size_t *bytes);
 int gcl_tcp_rx_acks(struct gcl_ctx *ctx, const struct gcl_rxack_in *in, const struct gcl_ctlseg_out *out,
                     uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/*
+ * The control segments of a gcl_tcp_rx_states call: gcl_tcp_rx_ctl stands
+ * where gcl_tcp_rx_acks stands and also emits the RSTs that send_rst
+ * (runtime/net/tcp_in.c:54-62) sends, in list order:
+ *
+ *   gcl_tcp_rx_states -> gcl_tcp_rx_ctl -> gcl_tx_hdr -> gcl_l4_csum GCL_L4_FILL
+ *
+ * @in is gcl_rxack_in's fields with its own size and ev and rst_seq as
+ * gcl_tcp_rx_states wrote them.  List entry j with verdict[j] ==
+ * GCL_TCPRX_FAST emits at most one segment (every send_rst path goes to done
+ * with do_ack false): an ACK when sflags[j] has GCL_TCPRX_SF_ACK_NOW, exactly
+ * as gcl_tcp_rx_acks writes it; else with GCL_TCPS_RST in ev[j] a gcl_txh_desc
+ * with proto 6, tcp_off 5, win 0, paylen 0, the tuple of addr[c], tcp_flags
+ * 0x04, seq = rst_seq[j] and ack 0 (tcp_tx_raw_rst, tcp_out.c:98-128), seg_kind
+ * GCL_CTL_RST; else with GCL_TCPS_RST_ACK tcp_flags 0x14, seq 0 and ack =
+ * rst_seq[j] (tcp_tx_raw_rst_ack, :139-170), seg_kind GCL_CTL_RST_ACK.  The
+ * guards (i below n, c below nconn), frame_off, seg_conn, seg_src = j, totals,
+ * seg_cap, the workspace, the three launches (decide, the scan of the block
+ * sums, emit) and @counts (GCL_RXACKC_WANTED, _WRITTEN, _SKIPPED) are
+ * gcl_tcp_rx_acks': on a list without RSTs the two calls write the same bytes.
+ * ev and rst_seq are among the arrays whose content causes no access outside
+ * the given arrays.  -EINVAL for what gcl_tcp_rx_acks refuses, and with m > 0
+ * a NULL ev or rst_seq, or a rst_seq that is not 4-B aligned.
+ */
+#define GCL_CTL_RST     2
+#define GCL_CTL_RST_ACK 3
+struct gcl_rxctl_in {
+	uint32_t size, blocks;             /* sizeof(struct gcl_rxctl_in) */
+	const uint32_t *order;
+	uint64_t m;
+	uint64_t n;
+	const uint32_t *sock;
+	const uint8_t  *verdict, *sflags;
+	const uint32_t *rcv_nxt_after;
+	const struct gcl_tcp_conn *conn;
+	const struct gcl_tcp_addr *addr;
+	uint32_t nconn;
+	uint32_t frame_stride;
+	uint64_t seg_cap;
+	uint64_t frame_base;
+	const uint8_t  *ev;                /* u8[m], as gcl_tcp_rx_states wrote it */
+	const uint32_t *rst_seq;           /* u32[m], as gcl_tcp_rx_states wrote it */
+};
+int gcl_tcp_rx_ctl_workspace(uint64_t m, uint32_t blocks, size_t *bytes);
+int gcl_tcp_rx_ctl(struct gcl_ctx *ctx, const struct gcl_rxctl_in *in, const struct gcl_ctlseg_out *out,
+                   uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /*
  * The TCP retransmit queue: where the three TCP chains meet.  gcl_tx_seg cuts
