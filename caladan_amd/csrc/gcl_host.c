@@ -15,6 +15,7 @@
 #include "gcl_tcprxf.h"
 #include "gcl_tcprxo.h"
 #include "gcl_tcprxs.h"
+#include "gcl_tcpopen.h"
 #include "gcl_tcptmr.h"
 #include "gcl_txq.h"
 #include "gcl_txh.h"
@@ -1628,6 +1629,144 @@ int gcl_tcp_rx_ctl_host(const struct gcl_rxctl_in *in, const struct gcl_ctlseg_o
 		counts[GCL_RXACKC_WRITTEN] += out->totals[1];
 		counts[GCL_RXACKC_SKIPPED] += skipped;
 	}
+	return 0;
+}
+
+/* The rule of gcl_tcp_rx_open (gclassify.h) on the CPU, taken literally: one
+ * walk over the list in order with the running backlog in backlog_out and the
+ * tuples accepted so far in an open-addressed table, gcl_open_head and
+ * gcl_open_walk of gcl_tcpopen.h for every entry. */
+int gcl_tcp_rx_open_host(const struct gcl_batch *b, const struct gcl_tcpopen_in *in,
+                         const struct gcl_tcpopen_out *out, const struct gcl_ctlseg_out *seg, uint64_t *counts)
+{
+	uint64_t c[GCL_OPENC_NR] = {0}, at = 0, nopen = 0;
+
+	if (gcl_open_refused(b, in, out, seg, counts))
+		return -EINVAL;
+	if (in->m == 0)
+		return 0;
+	const uint64_t lim = gcl_open_seg_lim(in->seg_cap, in->frame_base, in->frame_stride, in->tx_frames_len);
+	const uint64_t slots = in->hash_slots ? in->hash_slots : gcl_open_slots(in->m);
+	struct open_acc { uint32_t lip, rip, ports, listener, k; } *tbl = malloc(slots * sizeof(*tbl));
+
+	if (!tbl)
+		return -ENOMEM;
+	for (uint64_t x = 0; x < slots; x++)
+		tbl[x].k = GCL_OPEN_NONE;
+	for (uint32_t l = 0; l < in->nlisten; l++)
+		out->backlog_out[l] = in->listen[l].backlog;
+	for (uint64_t j = 0; j < in->m; j++) {
+		const uint64_t i = in->order ? in->order[j] : j;
+		struct gcl_open_ent e = {GCL_OPEN_OOR, 0, 0, 0, 0, 0, 0};
+		struct gcl_open_opts op = {0, 0, 0, 0};
+		uint32_t verdict, later = GCL_OPEN_NONE, l4[4] = {0, 0, 0, 0};
+		uint64_t o = 0, avail = 0;
+
+		if (i < b->n) {
+			const uint64_t raw = b->offs ? b->offs[i] : i * b->stride;
+			uint8_t h[56] = {0};
+			uint32_t d[11];
+
+			o = raw < b->frames_len ? raw : b->frames_len;
+			avail = b->frames_len - o;
+			const uint64_t L = b->pkt_len[i] < avail ? b->pkt_len[i] : avail;
+			if (avail)
+				memcpy(h, b->frames + o, avail < sizeof(h) ? avail : sizeof(h));
+			for (int x = 0; x < 11; x++)
+				d[x] = h[12 + 4 * x] | (uint32_t)h[13 + 4 * x] << 8 | (uint32_t)h[14 + 4 * x] << 16 |
+				       (uint32_t)h[15 + 4 * x] << 24;
+			e = gcl_open_head(d, L, in->l4_status != NULL, in->l4_status ? in->l4_status[i] : 0, in->sock[i],
+			                  in->listen_base, in->nlisten);
+		}
+		verdict = e.cls;
+		if (gcl_open_listener_route(e.cls)) {
+			uint64_t s = gcl_open_hash(e.lip, e.rip, e.ports, e.listener) & (slots - 1);
+
+			memcpy(l4, &in->listen[e.listener], sizeof(l4)); /* little-endian host */
+			while (tbl[s].k != GCL_OPEN_NONE && !(tbl[s].lip == e.lip && tbl[s].rip == e.rip &&
+			                                      tbl[s].ports == e.ports && tbl[s].listener == e.listener))
+				s = (s + 1) & (slots - 1); /* ACCEPTs <= m <= slots / 2: an empty slot exists */
+			later = tbl[s].k;
+			/* the running backlog is backlog minus the ACCEPTs so far: "before" = those */
+			verdict = gcl_open_final(e.cls, later != GCL_OPEN_NONE, gcl_open_l_flags(l4), gcl_open_l_backlog(l4),
+			                         gcl_open_l_backlog(l4) - out->backlog_out[e.listener]);
+			if (verdict == GCL_OPEN_ACCEPT) {
+				uint8_t ob[GCL_OPEN_MAX_OPT] = {0};
+				uint32_t w[10];
+
+				for (uint32_t x = 0; x < e.optlen; x++)
+					ob[x] = 54 + x < avail ? b->frames[o + 54 + x] : 0;
+				for (int x = 0; x < 10; x++)
+					w[x] = ob[4 * x] | (uint32_t)ob[4 * x + 1] << 8 | (uint32_t)ob[4 * x + 2] << 16 |
+					       (uint32_t)ob[4 * x + 3] << 24;
+				op = gcl_open_walk(w, e.optlen);
+				if (op.bad)
+					verdict = GCL_OPEN_BADOPT;
+			}
+			if (verdict == GCL_OPEN_ACCEPT) {
+				out->backlog_out[e.listener]--;
+				tbl[s].lip = e.lip;
+				tbl[s].rip = e.rip;
+				tbl[s].ports = e.ports;
+				tbl[s].listener = e.listener;
+				tbl[s].k = (uint32_t)j;
+			}
+		}
+		out->verdict[j] = (uint8_t)verdict;
+		out->later_of[j] = verdict == GCL_OPEN_LATER ? later : GCL_OPEN_NONE;
+		out->rst_seq[j] = verdict == GCL_OPEN_RST || verdict == GCL_OPEN_CLOSED_RST ||
+		                  verdict == GCL_OPEN_CLOSED_RST_ACK ? e.val : 0;
+		c[verdict]++;
+		if (verdict == GCL_OPEN_ACCEPT) {
+			uint32_t r[16], dd[8];
+
+			gcl_open_record(&e, &op, (uint32_t)j, in->iss[j], l4, r);
+			if (nopen < in->open_cap)
+				memcpy(&out->open[nopen], r, sizeof(out->open[nopen]));
+			else
+				c[GCL_OPENC_NOSPACE]++;
+			if (at < lim) {
+				uint8_t ob[8];
+				const uint32_t nb = gcl_open_optbytes(r, l4, ob);
+				const uint64_t fo = in->frame_base + at * in->frame_stride;
+
+				gcl_open_synack_desc(r, dd);
+				memcpy(&seg->desc[at], dd, sizeof(seg->desc[at]));
+				seg->frame_off[at] = fo;
+				seg->seg_conn[at] = (uint32_t)nopen;
+				seg->seg_kind[at] = GCL_CTL_SYNACK;
+				seg->seg_src[at] = (uint32_t)j;
+				for (uint32_t x = 0; x < nb; x++)
+					in->tx_frames[fo + 54 + x] = ob[x];
+			}
+			nopen++;
+			at++;
+		} else if (verdict == GCL_OPEN_RST || verdict == GCL_OPEN_CLOSED_RST || verdict == GCL_OPEN_CLOSED_RST_ACK) {
+			if (at < lim) {
+				const uint32_t a[4] = {e.lip, e.rip, e.ports, 0};
+				const uint32_t kind = verdict == GCL_OPEN_CLOSED_RST_ACK ? GCL_CTL_RST_ACK : GCL_CTL_RST;
+				uint32_t dd[8];
+
+				gcl_ctl_rst_desc(a, kind, e.val, dd);
+				memcpy(&seg->desc[at], dd, sizeof(seg->desc[at]));
+				seg->frame_off[at] = in->frame_base + at * in->frame_stride;
+				seg->seg_conn[at] = GCL_OPEN_NONE;
+				seg->seg_kind[at] = (uint8_t)kind;
+				seg->seg_src[at] = (uint32_t)j;
+			}
+			at++;
+		}
+	}
+	free(tbl);
+	out->totals[0] = nopen;
+	out->totals[1] = nopen < in->open_cap ? nopen : in->open_cap;
+	seg->totals[0] = at;
+	seg->totals[1] = at < lim ? at : lim;
+	c[GCL_OPENC_SEGS] = seg->totals[1];
+	c[GCL_OPENC_SEGSKIP] = at - seg->totals[1];
+	if (counts)
+		for (int k = 0; k < GCL_OPENC_NR; k++)
+			counts[k] += c[k];
 	return 0;
 }
 

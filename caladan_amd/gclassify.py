@@ -163,6 +163,23 @@ TCP_TMR_OUT_DTYPE = np.dtype([("next_timeout", "<u8"), ("zero_wnd_ts", "<u8"), (
                               ("action", "u1"), ("pad", "u1", (13,))])
 TCP_ADDR_DTYPE = np.dtype([("lip", "<u4"), ("rip", "<u4"), ("lport", "<u2"), ("rport", "<u2"),
                            ("rcv_wscale", "u1"), ("pad", "u1", (3,))])
+# gcl_tcp_rx_open: the verdicts (also their counter slots), the counters behind them, the caps, the
+# new segment kind, the listener flag, the option bits, struct gcl_tcp_listen and struct gcl_tcp_open
+(OPEN_NA, OPEN_OOR, OPEN_SHORT, OPEN_CLOSED_DROP, OPEN_CLOSED_RST, OPEN_CLOSED_RST_ACK, OPEN_LATER, OPEN_FULL,
+ OPEN_DROP, OPEN_RST, OPEN_BADOPT, OPEN_ACCEPT) = range(12)
+OPEN_NR_VERDICTS = 12
+OPENC_SEGS, OPENC_SEGSKIP, OPENC_NOSPACE, OPENC_NR = 12, 13, 14, 16
+OPEN_MAX_LISTEN, OPEN_MAX_BLOCKS, OPEN_NONE = 4096, 1024, 0xFFFFFFFF
+CTL_SYNACK = 4
+LISTEN_SHUTDOWN = 0x01
+OPEN_OPT_MSS, OPEN_OPT_WSCALE = 0x01, 0x02
+TCP_LISTEN_DTYPE = np.dtype([("backlog", "<u4"), ("winmax", "<u4"), ("rcv_mss", "<u2"), ("rcv_wscale", "u1"),
+                             ("flags", "u1"), ("pad", "<u4")])
+TCP_OPEN_DTYPE = np.dtype([("src", "<u4"), ("listener", "<u4"), ("lip", "<u4"), ("rip", "<u4"), ("lport", "<u2"),
+                           ("rport", "<u2"), ("irs", "<u4"), ("rcv_nxt", "<u4"), ("iss", "<u4"),
+                           ("snd_una", "<u4"), ("snd_nxt", "<u4"), ("rcv_wnd", "<u4"), ("winmax", "<u4"),
+                           ("snd_mss", "<u2"), ("snd_wscale", "u1"), ("rcv_wscale", "u1"), ("opt_en", "u1"),
+                           ("state", "u1"), ("pad", "u1", (10,))])
 # gcl_tcp_txq: the want bits, the entry flag, the state byte, the connection flags, the counters,
 # the caps, struct gcl_txq_ent, struct gcl_txq_cold and struct gcl_txq_conn_out
 TXQ_W_RTO, TXQ_W_FAST, TXQ_W_EXCL = 0x01, 0x02, 0x04
@@ -496,6 +513,22 @@ class GclRxctlIn(ctypes.Structure):
     _fields_ = GclRxackIn._fields_ + [("ev", ctypes.c_void_p), ("rst_seq", ctypes.c_void_p)]
 
 
+class GclTcpopenIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("order", ctypes.c_void_p),
+                ("m", ctypes.c_uint64), ("sock", ctypes.c_void_p), ("l4_status", ctypes.c_void_p),
+                ("hash_slots", ctypes.c_uint32), ("listen_base", ctypes.c_uint32), ("nlisten", ctypes.c_uint32),
+                ("frame_stride", ctypes.c_uint32), ("listen", ctypes.c_void_p), ("iss", ctypes.c_void_p),
+                ("seg_cap", ctypes.c_uint64), ("frame_base", ctypes.c_uint64), ("open_cap", ctypes.c_uint64),
+                ("tx_frames", ctypes.c_void_p), ("tx_frames_len", ctypes.c_uint64)]
+
+
+TCPOPEN_OUT_FIELDS = ("verdict", "later_of", "rst_seq", "open", "backlog_out", "totals")
+
+
+class GclTcpopenOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in TCPOPEN_OUT_FIELDS]
+
+
 class GclTxqIn(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("now", ctypes.c_uint64),
                 ("qoff", ctypes.c_void_p), ("ent", ctypes.c_void_p), ("cold", ctypes.c_void_p),
@@ -521,6 +554,8 @@ assert ctypes.sizeof(GclTcprxIn) == 56 and ctypes.sizeof(GclTcprxOut) == 56
 assert ctypes.sizeof(GclTcprxfIn) == 64 and TCP_CONN_EXT_DTYPE.itemsize == 16
 assert ctypes.sizeof(GclTcprxoIn) == 88 and ctypes.sizeof(GclTcprxoOut) == 72 and TCP_OOO_ENT_DTYPE.itemsize == 16
 assert ctypes.sizeof(GclRxctlIn) == 120
+assert ctypes.sizeof(GclTcpopenIn) == 112 and ctypes.sizeof(GclTcpopenOut) == 48
+assert TCP_LISTEN_DTYPE.itemsize == 16 and TCP_OPEN_DTYPE.itemsize == 64
 assert ctypes.sizeof(GclTcprxsIn) == 96 and ctypes.sizeof(GclTcprxsOut) == 32
 assert TCP_CONN_DTYPE.itemsize == 48 and TCP_CONN_OUT_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclSegIn) == 64 and ctypes.sizeof(GclSegOut) == 104 and SEG_SEND_DTYPE.itemsize == 48
@@ -658,6 +693,12 @@ def _load():
         "gcl_tcp_rx_acks": (i32, [vp, ctypes.POINTER(GclRxackIn), ctypes.POINTER(GclCtlsegOut), vp, vp,
                                   ctypes.c_size_t, vp]),
         "gcl_tcp_rx_acks_host": (i32, [ctypes.POINTER(GclRxackIn), ctypes.POINTER(GclCtlsegOut), vp]),
+        "gcl_tcp_rx_open_workspace": (i32, [u64, u32, u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_rx_open": (i32, [vp, ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcpopenIn),
+                                  ctypes.POINTER(GclTcpopenOut), ctypes.POINTER(GclCtlsegOut), vp, vp,
+                                  ctypes.c_size_t, vp]),
+        "gcl_tcp_rx_open_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcpopenIn),
+                                       ctypes.POINTER(GclTcpopenOut), ctypes.POINTER(GclCtlsegOut), vp]),
         "gcl_tcp_txq_workspace": (i32, [u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
         "gcl_tcp_txq": (i32, [vp, ctypes.POINTER(GclTxqIn), ctypes.POINTER(GclTxqOut), vp, vp,
                               ctypes.c_size_t, vp]),
@@ -1509,6 +1550,86 @@ def tcp_rx_ctl_workspace(m, blocks=0):
     """gcl_tcp_rx_ctl_workspace: bytes of device scratch a call over @m list entries takes."""
     need = ctypes.c_size_t()
     _check(lib.gcl_tcp_rx_ctl_workspace(m, blocks, ctypes.byref(need)), "gcl_tcp_rx_ctl_workspace")
+    return need.value
+
+
+def _tcpopen_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status, listen, nlisten,
+                     listen_base, iss, seg_cap, open_cap, frame_base, frame_stride, tx_frames, tx_frames_len,
+                     blocks, hash_slots, out, counts):
+    """The four structs of gcl_tcp_rx_open / gcl_tcp_rx_open_host, sizes
+    checked; @out maps TCPOPEN_OUT_FIELDS and CTLSEG_SEG_FIELDS to buffers and
+    "seg_totals" to the segments' totals."""
+    for arr, w in ((order, 4), (iss, 4), (out["verdict"], 1), (out["later_of"], 4), (out["rst_seq"], 4)):
+        if arr is not None and _nbytes(arr) < w * m:
+            raise ValueError("per-entry array too small")
+    for arr, w in ((sock, 4), (l4_status, 1), (pkt_len, 2)):
+        if arr is not None and _nbytes(arr) < w * n:
+            raise ValueError("per-packet array too small")
+    for arr, w in ((listen, 16), (out["backlog_out"], 4)):
+        if arr is not None and _nbytes(arr) < w * nlisten:
+            raise ValueError("per-listener array too small")
+    if out["open"] is not None and _nbytes(out["open"]) < 64 * open_cap:
+        raise ValueError("open shorter than open_cap")
+    for f in CTLSEG_SEG_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < CTLSEG_OUT_WIDTH[f] * seg_cap:
+            raise ValueError(f"{f}: per-segment array shorter than seg_cap")
+    for f in ("totals", "seg_totals"):
+        if out[f] is not None and _nbytes(out[f]) < 16:
+            raise ValueError("totals too small")
+    if counts is not None and _nbytes(counts) < 8 * OPENC_NR:
+        raise ValueError("counts buffer too small")
+    tx_frames_len = (0 if tx_frames is None else _nbytes(tx_frames)) if tx_frames_len is None else tx_frames_len
+    if tx_frames is not None and _nbytes(tx_frames) < tx_frames_len:
+        raise ValueError("tx_frames shorter than tx_frames_len")
+    b = GclBatch(frames=_ptr(frames), frames_len=_frames_len(frames, frames_len), stride=stride,
+                 offs=_ptr(offs), olflags=None, rss=None, fdir_hi=None, pkt_len=_ptr(pkt_len), n=n,
+                 dst_hint=None)
+    oin = GclTcpopenIn(size=ctypes.sizeof(GclTcpopenIn), blocks=blocks, order=_ptr(order), m=m, sock=_ptr(sock),
+                       l4_status=_ptr(l4_status), hash_slots=hash_slots, listen_base=listen_base, nlisten=nlisten,
+                       frame_stride=frame_stride, listen=_ptr(listen), iss=_ptr(iss), seg_cap=seg_cap,
+                       frame_base=frame_base, open_cap=open_cap, tx_frames=_ptr(tx_frames),
+                       tx_frames_len=tx_frames_len)
+    oout = GclTcpopenOut(**{f: _ptr(out[f]) for f in TCPOPEN_OUT_FIELDS})
+    seg = GclCtlsegOut(**{f: _ptr(out[f]) for f in CTLSEG_SEG_FIELDS}, totals=_ptr(out["seg_totals"]))
+    return b, oin, oout, seg
+
+
+def tcp_rx_open_host(frames, pkt_len, sock, listen, iss, seg_cap, open_cap, tx_frames, stride=0, offs=None, n=None,
+                     frames_len=None, order=None, m=None, l4_status=None, nlisten=None, listen_base=0,
+                     frame_stride=64, frame_base=0, tx_frames_len=None, blocks=0, hash_slots=0, out=None,
+                     counts=None):
+    """gcl_tcp_rx_open_host: the rule of Classifier.tcp_rx_open on the CPU over
+    numpy arrays.  @listen is a TCP_LISTEN_DTYPE array, cookie listen_base + l
+    naming listen[l]; @iss a u32[m]; @tx_frames the uint8 tx region, written in
+    place (the option bytes of the SYN|ACKs).  @out maps TCPOPEN_OUT_FIELDS
+    (u8[m], u32[m], u32[m], TCP_OPEN_DTYPE[open_cap], u32[nlisten], u64[2]),
+    CTLSEG_SEG_FIELDS (each @seg_cap long) and "seg_totals" (u64[2]) to arrays;
+    the ones left out are allocated.  @counts is a u64[OPENC_NR], accumulated.
+    Returns the dict."""
+    n = len(pkt_len) if n is None else n
+    m = _pay_m(n, m, order)
+    nlisten = len(listen) if nlisten is None else nlisten
+    out = dict(out or {})
+    for f, dt, k in (("verdict", np.uint8, m), ("later_of", np.uint32, m), ("rst_seq", np.uint32, m),
+                     ("open", TCP_OPEN_DTYPE, open_cap), ("backlog_out", np.uint32, nlisten),
+                     ("totals", np.uint64, 2), ("seg_totals", np.uint64, 2), ("desc", TXH_DESC_DTYPE, seg_cap),
+                     ("frame_off", np.uint64, seg_cap), ("seg_conn", np.uint32, seg_cap),
+                     ("seg_kind", np.uint8, seg_cap), ("seg_src", np.uint32, seg_cap)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    b, oin, oout, seg = _tcpopen_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status,
+                                         listen, nlisten, listen_base, iss, seg_cap, open_cap, frame_base,
+                                         frame_stride, tx_frames, tx_frames_len, blocks, hash_slots, out, counts)
+    _check(lib.gcl_tcp_rx_open_host(ctypes.byref(b), ctypes.byref(oin), ctypes.byref(oout), ctypes.byref(seg),
+                                    _ptr(counts)), "gcl_tcp_rx_open_host")
+    return out
+
+
+def tcp_rx_open_workspace(m, nlisten, blocks=0, hash_slots=0):
+    """gcl_tcp_rx_open_workspace: bytes of device scratch a call over @m list entries and @nlisten listeners takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_rx_open_workspace(m, nlisten, blocks, hash_slots, ctypes.byref(need)),
+           "gcl_tcp_rx_open_workspace")
     return need.value
 
 
@@ -2375,6 +2496,49 @@ class Classifier:
                                                                    out["totals"].device)
         _check(lib.gcl_tcp_rx_ctl(self._ctx, ctypes.byref(cin), ctypes.byref(rout), _ptr(counts), _ptr(ws),
                                   _nbytes(ws), stream), "gcl_tcp_rx_ctl")
+        return out
+
+    def tcp_rx_open(self, frames, n, pkt_len, sock, m, listen, nlisten, iss, seg_cap, open_cap, tx_frames,
+                    stride=0, offs=None, frames_len=None, order=None, l4_status=None, listen_base=0,
+                    frame_stride=64, frame_base=0, tx_frames_len=None, blocks=0, hash_slots=0, out=None,
+                    counts=None, workspace=None, stream=None):
+        """gcl_tcp_rx_open: the passive open of one runtime's list on the GPU,
+        asynchronous: tcp_rx_listener for the packets of listeners (cookies
+        listen_base .. listen_base + nlisten) and tcp_rx_closed for
+        SOCK_MISS, with the new connections, their SYN|ACKs and the RSTs.
+        @listen is a device uint8[nlisten, 16] of TCP_LISTEN_DTYPE records,
+        @iss a device int32[m], @tx_frames the device tx region (the option
+        bytes of the SYN|ACKs are written into it).  @out maps
+        TCPOPEN_OUT_FIELDS, CTLSEG_SEG_FIELDS and "seg_totals" to device
+        buffers; the ones left out are allocated on @sock's device (open
+        uint8[open_cap, 64]).  @counts is a device u64[OPENC_NR], accumulated.
+        Returns the dict: desc and frame_off are tx_hdr's, seg_totals[1] its
+        m; open[0:totals[1]] are the connections to install."""
+        import torch
+        dev = sock.device
+        out = dict(out or {})
+        sc, oc = max(seg_cap, 1), max(open_cap, 1)
+        for f, dt, shape in (("verdict", torch.uint8, (max(m, 1),)), ("later_of", torch.int32, (max(m, 1),)),
+                             ("rst_seq", torch.int32, (max(m, 1),)), ("open", torch.uint8, (oc, 64)),
+                             ("backlog_out", torch.int32, (max(nlisten, 1),)), ("totals", torch.int64, (2,)),
+                             ("seg_totals", torch.int64, (2,)), ("desc", torch.uint8, (sc, 32)),
+                             ("frame_off", torch.int64, (sc,)), ("seg_conn", torch.int32, (sc,)),
+                             ("seg_kind", torch.uint8, (sc,)), ("seg_src", torch.int32, (sc,))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        b, oin, oout, seg = _tcpopen_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock,
+                                             l4_status, listen, nlisten, listen_base, iss, seg_cap, open_cap,
+                                             frame_base, frame_stride, tx_frames, tx_frames_len, blocks,
+                                             hash_slots, out, counts)
+        if workspace is None:
+            need = tcp_rx_open_workspace(m, nlisten, blocks, hash_slots)
+            ws = getattr(self, "_open_ws_buf", None)
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = self._open_ws_buf = torch.empty(need, dtype=torch.uint8, device=dev)
+            workspace = ws
+        _check(lib.gcl_tcp_rx_open(self._ctx, ctypes.byref(b), ctypes.byref(oin), ctypes.byref(oout),
+                                   ctypes.byref(seg), _ptr(counts), _ptr(workspace), _nbytes(workspace), stream),
+               "gcl_tcp_rx_open")
         return out
 
     def tcp_txq(self, now, qoff, ent, cold, nent, conn, addr, nconn, seg_cap, want=None, frame_stride=64,

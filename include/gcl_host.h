@@ -316,6 +316,20 @@ int gcl_tcp_rx_ctl_host(const struct gcl_rxctl_in *in, const struct gcl_ctlseg_o
 int gcl_tcp_rx_acks_host(const struct gcl_rxack_in *in, const struct gcl_ctlseg_out *out, uint64_t *counts);
 
 /*
+ * gcl_tcp_rx_open_host - the rule of gcl_tcp_rx_open (gclassify.h) on the CPU
+ * over host pointers, taken literally: one walk over the list in order with
+ * the running backlog and a table of the tuples accepted so far, the
+ * per-entry rule and the option walk being the inline code of
+ * csrc/gcl_tcpopen.h that the kernels run.  in->blocks and in->hash_slots are
+ * checked (hash_slots sizes the twin's own table too).  @counts is a host
+ * u64[GCL_OPENC_NR], ACCUMULATED, may be NULL.  The same outputs byte for
+ * byte, the same counts and the same guarantee.  0, -EINVAL for what the call
+ * refuses (the ctx and the workspace apart), or -ENOMEM.
+ */
+int gcl_tcp_rx_open_host(const struct gcl_batch *b, const struct gcl_tcpopen_in *in,
+                         const struct gcl_tcpopen_out *out, const struct gcl_ctlseg_out *seg, uint64_t *counts);
+
+/*
  * gcl_tcp_txq_host - the rule of gcl_tcp_txq (gclassify.h) on the CPU over
  * host pointers, for the queues the GPU did not see: tcp_conn_ack
  * (runtime/net/tcp.c:217-238), tcp_tx_retransmit with tcp_tx_retransmit_one

@@ -2721,6 +2721,227 @@ int gcl_tcp_txq_workspace(uint32_t nconn, uint32_t blocks, size_t *bytes);
 int gcl_tcp_txq(struct gcl_ctx *ctx, const struct gcl_txq_in *in, const struct gcl_txq_out *out,
                 uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/*
+ * The passive open: the two answers of gcl_sock_lookup that no other call
+ * takes.  A TCP packet whose cookie is a listener goes to tcp_queue_recv ->
+ * tcp_rx_listener (runtime/net/tcp.c:488-522, runtime/net/tcp_in.c:614-694),
+ * one whose lookup missed to net_rx_trans -> tcp_rx_closed (runtime/net/
+ * transport.c:413-419, tcp_in.c:696-723).  gcl_tcp_rx_open runs one runtime's
+ * list through both and writes the new connections, their SYN|ACKs with the
+ * option bytes, and the RSTs a closed port or a listener answers:
+ *
+ *   gcl_classify -> gcl_sock_lookup -> gcl_l4_csum VERIFY -> gcl_plan ->
+ *   { gcl_tcp_rx_states -> gcl_tcp_rx_ctl,  gcl_tcp_rx_open } -> gcl_tx_hdr ->
+ *   gcl_l4_csum GCL_L4_FILL
+ *
+ * List entry j names packet i = in->order ? in->order[j] : j.  o, avail, L and
+ * tot are gcl_l4_csum's, frames are addressed as gcl_l4_payload addresses them
+ * (b->pkt_len REQUIRED), a byte at or past frames_len reads 0.  A packet is
+ * TCP-ELIGIBLE when it is L4-eligible as gcl_l4_csum says with protocol 6,
+ * except that tot need only be 20 (net_rx_one's length test): line 3 is where
+ * the reference finds the TCP header too short.  Cookie c with listen_base <=
+ * c < listen_base + nlisten (and c <= GCL_SOCK_COOKIE_MAX) is listener
+ * c - listen_base; the cookie namespace is the caller's.  seq, ack, off and
+ * flags are frame bytes 38-41, 42-45, 46 >> 4 and 47; lip / lport are the
+ * packet's daddr / dport, rip / rport its saddr / sport.  verdict[j] is the
+ * first line that matches:
+ *   1. i >= b->n                                              GCL_OPEN_OOR
+ *   2. sock[i] is neither GCL_SOCK_MISS nor a listener cookie
+ *      (GCL_SOCK_NA, connections, GCL_SOCK_MULTI: the runtime
+ *      picks among reuse_port listeners by thread id), the
+ *      packet is not TCP-eligible, or l4_status is given and
+ *      says GCL_L4_BAD (what gcl_tcp_rx would not take)       GCL_OPEN_NA
+ *   3. tot - 20 < 20 or L < 54: mbuf_pull_hdr_or_null fails   GCL_OPEN_SHORT
+ *   4. GCL_SOCK_MISS, tcp_rx_closed (tcp_in.c:708-722):
+ *      RST                                                    GCL_OPEN_CLOSED_DROP
+ *      ACK: rst_seq[j] = ack                                  GCL_OPEN_CLOSED_RST
+ *      else: rst_seq[j] = seq + (tot - 20 - 4 * off) mod 2^32,
+ *        as written: not checked against wrap, SYN and FIN
+ *        not counted                                          GCL_OPEN_CLOSED_RST_ACK
+ *   5. listener l, the entries taken in list order:
+ *      a. an earlier entry k < j with verdict ACCEPT has the
+ *         same (lip, lport, rip, rport) and listener:
+ *         later_of[j] = k.  tcp_conn_attach made k's connection
+ *         the 5-tuple match of this packet, whatever its flags;
+ *         the backlog is not touched.  The caller runs it
+ *         through gcl_tcp_rx_states once open[] is installed    GCL_OPEN_LATER
+ *      b. GCL_LISTEN_SHUTDOWN, or the running backlog is 0
+ *         (tcp.c:496): listen[l].backlog minus the ACCEPTs of l
+ *         before j; every other outcome gives its slot back
+ *         (:505-509).  Silent: an ACK gets no RST here          GCL_OPEN_FULL
+ *      c. tcp_rx_listener (tcp_in.c:638-656): RST               GCL_OPEN_DROP
+ *         ACK: rst_seq[j] = ack                                 GCL_OPEN_RST
+ *         no SYN; tot - 20 != 4 * off (off < 5, or a SYN with
+ *         data); an option byte at or past L                    GCL_OPEN_DROP
+ *      d. tcp_parse_options meets an option other than EOL or
+ *         NOP whose length byte is 0                            GCL_OPEN_BADOPT
+ *      e. otherwise                                             GCL_OPEN_ACCEPT
+ * (The listener is part of 5a's comparison.  gcl_sock_lookup gives one tuple
+ * one listener, so this matters only for a sock array that is not its.)
+ * Line 5d is the ONE PLACE THE CALL DECLINES TO FOLLOW THE REFERENCE: on that
+ * input tcp_parse_options does not return (ptr += opsize - 2; len -= opsize
+ * makes no progress), so there is nothing to follow.
+ *
+ * The option walk is tcp_parse_options (tcp_in.c:298-348) as written over the
+ * 4 * off - 20 option bytes: EOL stops it, NOP takes one byte, MSS counts only
+ * with length 4, WSCALE only with length 3 and is clamped to 14, any other
+ * length still advances by that length (a length of 1 steps back onto the
+ * length byte), the last occurrence wins, len may go negative and that ends
+ * the walk.  A read at or past the end of the option bytes reads 0 (the
+ * reference reads what follows in the mbuf; the two differ only on malformed
+ * options), so an opcode in the last byte is line 5d.  Then snd_mss =
+ * min(max(mss, 88), rcv_mss), or 1460 (tcp_calculate_mss(ETH_DEFAULT_MTU))
+ * when no MSS counted; snd_wscale the clamped value or 0; without WSCALE
+ * rcv_wnd = winmax = min(winmax, 65535) and rcv_wscale = 0, with it rcv_wnd =
+ * winmax and rcv_wscale as the listener gives it; opt_en the options that
+ * counted.  snd_wscale and the WSCALE bit are pinned to the reference's own
+ * tcp_in.c; snd_mss is not visible through that driver and rests on the tests'
+ * independent model and hand-derived cases.
+ *
+ * An ACCEPT writes open[k], k counting the ACCEPTs in list order: src = j,
+ * irs = seq, rcv_nxt = irs + 1, iss = in->iss[j] (read only for an ACCEPT),
+ * snd_una = iss, snd_nxt = iss + 1 (after tcp_tx_ctl), state SYN_RECEIVED, pad
+ * 0: what gcl_sock_entry, gcl_tcp_conn, gcl_tcp_addr and gcl_tcp_tmr.state
+ * need to install the connection before the next batch.  totals[0] = the
+ * ACCEPTs, totals[1] = min(ACCEPTs, open_cap); a record at or past open_cap
+ * is not written, its entry is an ACCEPT all the same and counts in
+ * GCL_OPENC_NOSPACE.  backlog_out[l] = listen[l].backlog minus l's ACCEPTs.
+ * later_of[j] is 0xFFFFFFFF and rst_seq[j] 0 where the rule names none.
+ *
+ * Segments go through @seg in list order, at most one per entry, segment k at
+ * frame_off = frame_base + k * frame_stride (mod 2^64), seg_src = j:
+ *   GCL_OPEN_RST, GCL_OPEN_CLOSED_RST      GCL_CTL_RST, and
+ *   GCL_OPEN_CLOSED_RST_ACK                GCL_CTL_RST_ACK, the gcl_txh_desc
+ *     exactly as gcl_tcp_rx_ctl writes the two kinds, with lip = the packet's
+ *     own daddr and rip its saddr; seg_conn 0xFFFFFFFF
+ *   GCL_OPEN_ACCEPT                        GCL_CTL_SYNACK: proto 6, tcp_flags
+ *     0x12, seq = iss, ack = irs + 1, paylen 0, tcp_off = 5 + the options in
+ *     opt_en, win = (uint16_t)(rcv_wnd >> (rcv_wscale & 31)) (tcp_out.c:74);
+ *     seg_conn = the index into open[].  gcl_tx_hdr leaves the option bytes
+ *     to its caller, so this call writes them at tx_frames[frame_off + 54 ..]
+ *     in tcp_put_options' order (tcp_out.c:230-251): 01 03 03 rcv_wscale when
+ *     WSCALE is enabled, then 02 04 hi(rcv_mss) lo(rcv_mss) when MSS is; one
+ *     byte store each, and nothing else in the frame.
+ * Segment k is written exactly when k < seg_cap and its slot [frame_off,
+ * frame_off + frame_stride) lies inside tx_frames_len, which with an
+ * increasing frame_off is k < (tx_frames_len - frame_base) / frame_stride; a
+ * frame_base past tx_frames_len writes none.  seg->totals[0] = the segments
+ * wanted, [1] = those written, the m of gcl_tx_hdr; the others count in
+ * GCL_OPENC_SEGSKIP.  frame_stride is at least GCL_CTL_MIN_STRIDE + 8.
+ *
+ * @counts is a device u64[GCL_OPENC_NR], ACCUMULATED, may be NULL: one slot
+ * per verdict (slot = verdict; per call they sum to m), SEGS (written),
+ * SEGSKIP and NOSPACE.  in->blocks: 0 is the library's choice, else the number
+ * of contiguous ranges the list is cut into; in->hash_slots: 0 is the
+ * library's choice, else the power-of-two size of the tuple table, at least
+ * 2 * m (both for tests).  The result depends on neither,
+ * nor on which lane wins a race: the tuple table keeps the smallest list
+ * index of every tuple, per-listener counts are sums, and positions come from
+ * scans.
+ *
+ * Every pointer is a device pointer; each array is aligned to its element,
+ * listen and open to 16 B.  Asynchronous on @hip_stream, launches ordered by
+ * the stream alone, no allocation, no host synchronisation.  @workspace
+ * (device, 16-B aligned) need not be zeroed.  m == 0 is a no-op.
+ *
+ * Guarantee: no content of frames, offs, pkt_len, order, sock, l4_status,
+ * listen or iss causes a read outside frames[0, frames_len) and the given
+ * arrays, or a write outside the m-element outputs, open[0, open_cap),
+ * backlog_out[0, nlisten), the first seg_cap elements of the segment arrays,
+ * the totals, counts, the workspace and the option bytes named above.  The
+ * walk is bounded: at most 40 option bytes.
+ *
+ * What stays with the runtime: tcp_conn_alloc's memory and iss, installing
+ * open[] (gcl_sock_set, the conn / addr / tmr arrays, the accept queue and its
+ * wake-up), replaying LATER entries, SYN_SENT (the active open), and reuse_port.
+ *
+ * gcl_tcp_rx_open_workspace - bytes of device scratch a call takes.  -EINVAL
+ *   for a NULL @bytes, m > 2^31, nlisten > GCL_OPEN_MAX_LISTEN, blocks >
+ *   GCL_OPEN_MAX_BLOCKS, or a hash_slots that is neither 0 nor a power of two
+ *   of at least 2 * m.
+ * gcl_tcp_rx_open - -EINVAL for a NULL ctx, b, in, out or seg; a wrong
+ *   in->size; order == NULL with m != b->n; what the workspace call refuses;
+ *   seg_cap or open_cap > 2^31; frame_stride < GCL_CTL_MIN_STRIDE + 8; a NULL
+ *   seg->totals or out->totals; with nlisten > 0 a NULL listen or
+ *   backlog_out; with m > 0 a NULL sock, iss, verdict, later_of or rst_seq,
+ *   with open_cap > 0 also a NULL open, with seg_cap > 0 a NULL per-segment
+ *   array, with tx_frames_len > 0 a NULL tx_frames; any given array that is
+ *   not aligned to its element; a NULL workspace, one that is not 16-B
+ *   aligned or one that is too small; and, when m > 0, what gcl_l4_payload
+ *   refuses of a batch.  -EIO when a launch fails.
+ */
+/* verdict[j], and the counter slot of each */
+#define GCL_OPEN_NA             0
+#define GCL_OPEN_OOR            1
+#define GCL_OPEN_SHORT          2
+#define GCL_OPEN_CLOSED_DROP    3
+#define GCL_OPEN_CLOSED_RST     4
+#define GCL_OPEN_CLOSED_RST_ACK 5
+#define GCL_OPEN_LATER          6
+#define GCL_OPEN_FULL           7
+#define GCL_OPEN_DROP           8
+#define GCL_OPEN_RST            9
+#define GCL_OPEN_BADOPT         10
+#define GCL_OPEN_ACCEPT         11
+#define GCL_OPEN_NR_VERDICTS    12
+enum { GCL_OPENC_SEGS = 12, GCL_OPENC_SEGSKIP, GCL_OPENC_NOSPACE, GCL_OPENC_NR = 16 };
+#define GCL_OPEN_MAX_LISTEN 4096   /* the cap on in->nlisten */
+#define GCL_OPEN_MAX_BLOCKS 1024   /* the cap on in->blocks */
+#define GCL_CTL_SYNACK      4      /* seg_kind[k] beside GCL_CTL_ACK .. GCL_CTL_RST_ACK */
+#define GCL_TCP_STATE_SYN_RECEIVED 1
+#define GCL_LISTEN_SHUTDOWN 0x01   /* gcl_tcp_listen.flags: q->shutdown */
+/* gcl_tcp_open.opt_en: TCP_OPTION_MSS and TCP_OPTION_WSCALE (runtime/net/tcp.h:165-166) */
+#define GCL_OPEN_OPT_MSS    0x01
+#define GCL_OPEN_OPT_WSCALE 0x02
+struct gcl_tcp_listen {    /* 16 B, 16-B aligned, host order: one listener */
+	uint32_t backlog;      /* q->backlog on entry */
+	uint32_t winmax;       /* tcp_default_win */
+	uint16_t rcv_mss;      /* tcp_calculate_mss(net_get_mtu()) */
+	uint8_t  rcv_wscale;   /* tcp_scale_window(winmax) */
+	uint8_t  flags;        /* GCL_LISTEN_* */
+	uint32_t pad;
+};
+struct gcl_tcp_open {      /* 64 B, 16-B aligned, host order: the connection an ACCEPT opens */
+	uint32_t src;          /* the list position j of its SYN */
+	uint32_t listener;
+	uint32_t lip, rip;
+	uint16_t lport, rport;
+	uint32_t irs, rcv_nxt, iss;
+	uint32_t snd_una, snd_nxt, rcv_wnd, winmax;
+	uint16_t snd_mss;
+	uint8_t  snd_wscale, rcv_wscale;
+	uint8_t  opt_en;       /* GCL_OPEN_OPT_* */
+	uint8_t  state;        /* GCL_TCP_STATE_SYN_RECEIVED */
+	uint8_t  pad[10];      /* written as 0 */
+};
+struct gcl_tcpopen_in {
+	uint32_t size, blocks;             /* sizeof(struct gcl_tcpopen_in) */
+	const uint32_t *order;             /* optional u32[m]; NULL: m == b->n and i = j */
+	uint64_t m;                        /* list entries, <= 2^31 */
+	const uint32_t *sock;              /* u32[b->n], as gcl_sock_lookup wrote it */
+	const uint8_t  *l4_status;         /* optional u8[b->n], as GCL_L4_VERIFY wrote it */
+	uint32_t hash_slots;               /* 0: the library's choice */
+	uint32_t listen_base, nlisten;
+	uint32_t frame_stride;             /* bytes, >= GCL_CTL_MIN_STRIDE + 8 */
+	const struct gcl_tcp_listen *listen; /* [nlisten] */
+	const uint32_t *iss;               /* u32[m]: the pcb.iss tcp_conn_alloc would draw for entry j */
+	uint64_t seg_cap, frame_base;      /* as in gcl_rxctl_in */
+	uint64_t open_cap;                 /* <= 2^31: the length of open[] */
+	uint8_t *tx_frames;                /* the tx region gcl_tx_hdr will be given */
+	uint64_t tx_frames_len;
+};
+struct gcl_tcpopen_out {               /* device, aligned to their element */
+	uint8_t  *verdict;                 /* [m] */
+	uint32_t *later_of, *rst_seq;      /* [m] */
+	struct gcl_tcp_open *open;         /* [open_cap] */
+	uint32_t *backlog_out;             /* [nlisten] */
+	uint64_t *totals;                  /* u64[2], required: opens wanted, written */
+};
+int gcl_tcp_rx_open_workspace(uint64_t m, uint32_t nlisten, uint32_t blocks, uint32_t hash_slots, size_t *bytes);
+int gcl_tcp_rx_open(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct gcl_tcpopen_in *in,
+                    const struct gcl_tcpopen_out *out, const struct gcl_ctlseg_out *seg, uint64_t *counts,
+                    void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
