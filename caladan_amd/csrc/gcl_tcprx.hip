@@ -44,10 +44,20 @@
  *            (only with counts) sums the connections' counters: an add per
  *            counter per block.
  *
- * gcl_tcp_rx_full (the rule of gcl_tcprxf.h) shares every launch but three:
- * its walk is serial over the chunk (rxf_walk_kernel), its fix-up keys on
- * copy_len, and its counter kernel sums ten counters; both entry points go
- * through rx_run, and gcl_tcp_rx launches what it always launched.
+ * The four calls (gcl_tcp_rx, _full, _ooo, _states) go through one driver,
+ * rx_run.  Shared by all: parse, group, runs and the layout scan.  A call's
+ * own:
+ *   walk     gcl_tcp_rx: rx_walk_kernel.  _full: rxf_walk_kernel, serial over
+ *            the chunk (gcl_tcprxf.h).  _ooo and _states: the two
+ *            instantiations of rxq_walk_kernel, which lists what differs
+ *            between them; then a scan of the final queue lengths.
+ *   fix-up   rx_fix_kernel keyed on the verdict for gcl_tcp_rx, on copy_len
+ *            for the other three.
+ *   queues   _ooo and _states: rxo_qout_kernel.
+ *   counters rx_counts_kernel over 5, 10 or 16 counters (_ooo and _states
+ *            share the 16; _states' four more are added by its walk).
+ * The walks share the connection load, the run bounds, the chunk gather and
+ * the per-connection stores; the three serial walks also the chunk's end.
  *
  * Bounds.  A list index is used only below m, a packet index only below n, a
  * cookie only below nconn (parse leaves no other in the workspace, and every
@@ -63,6 +73,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/gclassify.h"
 #include "gcl_ctx.h"
@@ -466,35 +477,79 @@ __device__ __forceinline__ uint32_t rx_lane(uint32_t v, uint32_t l)
 	return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
 }
 
+/* the connection this wave walks: wave-uniform */
+__device__ __forceinline__ uint32_t rx_wave_conn()
+{
+	return (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRxWaves + (threadIdx.x >> 6)));
+}
+
+__device__ __forceinline__ struct gcl_tcp_conn rx_conn_load(const RxParams &k, uint32_t c)
+{
+	const uint4 a = k.conn[3 * (size_t)c], b = k.conn[3 * (size_t)c + 1], d = k.conn[3 * (size_t)c + 2];
+	struct gcl_tcp_conn cn;
+
+	cn.snd_una = a.x; cn.snd_nxt = a.y; cn.snd_wnd = a.z; cn.snd_wl1 = a.w;
+	cn.snd_wl2 = b.x; cn.rcv_nxt = b.y; cn.rcv_wnd = b.z;
+	cn.rcv_mss = (uint16_t)b.w; cn.snd_wscale = (uint8_t)(b.w >> 16); cn.flags = (uint8_t)(b.w >> 24);
+	cn.acks_delayed_cnt = (uint8_t)d.x;
+	return cn;
+}
+
+/* connection c's run of sorted positions [*rs, *re): both at most m whatever the workspace holds */
+__device__ __forceinline__ void rx_run_bounds(const RxParams &k, uint32_t c, uint64_t *rs, uint64_t *re)
+{
+	const uint2 rn = k.run[c];
+
+	*re = rn.y < k.m ? rn.y : k.m;
+	*rs = rn.x < *re ? rn.x : *re;
+}
+
+/* up to 64 entries of a run from @base on, entry i in lane i: its list position (below m) and its record */
+struct RxChunk {
+	uint32_t nv, j;
+	bool valid;
+	uint4 rec;
+};
+
+__device__ __forceinline__ RxChunk rx_gather(const RxParams &k, const uint32_t *sorted, uint64_t base, uint64_t re,
+                                             uint32_t lane)
+{
+	RxChunk ch;
+
+	ch.nv = re - base < 64 ? (uint32_t)(re - base) : 64;
+	ch.valid = lane < ch.nv;
+	ch.j = ch.valid ? sorted[base + lane] : 0;
+	if (ch.j >= k.m)
+		ch.j = (uint32_t)(k.m - 1);
+	ch.rec = ch.valid ? k.rec[ch.j] : make_uint4(0, 0, 0, 0);
+	return ch;
+}
+
+/* struct gcl_tcp_conn_out of connection c; one lane calls it */
+__device__ __forceinline__ void rx_conn_store(const RxParams &k, uint32_t c, const struct gcl_tcprx_live &l,
+                                              uint32_t nfast, uint32_t nslow, uint32_t nacks, uint32_t first_slow)
+{
+	k.out_conn[3 * (size_t)c] = make_uint4(l.snd_una, l.snd_wnd, l.snd_wl1, l.snd_wl2);
+	k.out_conn[3 * (size_t)c + 1] = make_uint4(l.rcv_nxt, l.rcv_wnd, nfast, nslow);
+	k.out_conn[3 * (size_t)c + 2] = make_uint4(nacks, first_slow, (l.cnt & 0xFFu) | (l.flags & 0xFFu) << 8, 0);
+}
+
 __global__ void __launch_bounds__(kRxThreads) rx_walk_kernel(RxParams k, const uint32_t *sorted)
 {
 	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRxWaves + (threadIdx.x >> 6)));
+	const uint32_t c = rx_wave_conn();
 
 	if (c >= k.nconn)
 		return;
-	struct gcl_tcp_conn cn;
-	{
-		const uint4 a = k.conn[3 * (size_t)c], b = k.conn[3 * (size_t)c + 1], d = k.conn[3 * (size_t)c + 2];
-		cn.snd_una = a.x; cn.snd_nxt = a.y; cn.snd_wnd = a.z; cn.snd_wl1 = a.w;
-		cn.snd_wl2 = b.x; cn.rcv_nxt = b.y; cn.rcv_wnd = b.z;
-		cn.rcv_mss = (uint16_t)b.w; cn.snd_wscale = (uint8_t)(b.w >> 16); cn.flags = (uint8_t)(b.w >> 24);
-		cn.acks_delayed_cnt = (uint8_t)d.x;
-	}
+	const struct gcl_tcp_conn cn = rx_conn_load(k, c);
 	struct gcl_tcprx_live l = gcl_tcprx_live_of(&cn);
-	const uint2 rn = k.run[c];
-	const uint64_t re = rn.y < k.m ? rn.y : k.m;
-	const uint64_t rs = rn.x < re ? rn.x : re;
+	uint64_t rs, re;
+	rx_run_bounds(k, c, &rs, &re);
 	uint32_t nfast = 0, nslow = 0, nacks = 0, wakes = 0, first_slow = GCL_TCPRX_NONE;
 
 	for (uint64_t base = rs; base < re; base += 64) { /* uniform */
-		const uint32_t nv = re - base < 64 ? (uint32_t)(re - base) : 64;
-		const bool valid = lane < nv;
-		uint32_t j = valid ? sorted[base + lane] : 0;
-		if (j >= k.m)
-			j = (uint32_t)(k.m - 1);
-		const uint4 rec = valid ? k.rec[j] : make_uint4(0, 0, 0, 0);
-		const uint32_t seq = rec.x, ack = rec.y, win = rec.z & 0xFFFFu, flags = rec.z >> 16, len = rec.w;
+		const RxChunk ch = rx_gather(k, sorted, base, re, lane);
+		const uint32_t seq = ch.rec.x, ack = ch.rec.y, win = ch.rec.z & 0xFFFFu, flags = ch.rec.z >> 16, len = ch.rec.w;
 		const bool stopped = (l.flags & GCL_TCPO_STOPPED) != 0;
 
 		/* the sum of len over the lanes below: the chain's rcv_nxt and rcv_wnd at this lane */
@@ -505,7 +560,7 @@ __global__ void __launch_bounds__(kRxThreads) rx_walk_kernel(RxParams k, const u
 				incl += u;
 		}
 		const uint32_t excl = incl - len;
-		const bool bad = !valid || gcl_tcprx_slow_fixed(flags, len, ack, cn.snd_nxt, cn.flags) ||
+		const bool bad = !ch.valid || gcl_tcprx_slow_fixed(flags, len, ack, cn.snd_nxt, cn.flags) ||
 		                 gcl_tcprx_slow_rcv(seq, len, l.rcv_nxt + excl, l.rcv_wnd - excl);
 		const uint64_t badmask = __ballot(bad);
 		uint32_t F = stopped ? 0 : badmask ? (uint32_t)__builtin_ctzll(badmask) : 64;
@@ -527,73 +582,43 @@ __global__ void __launch_bounds__(kRxThreads) rx_walk_kernel(RxParams k, const u
 			wakes += (sf & GCL_TCPRX_SF_WAKE) != 0;
 		}
 		nfast += F;
-		nslow += nv - F;
-		if (F < nv) {
+		nslow += ch.nv - F;
+		if (F < ch.nv) {
 			if (!stopped)
-				first_slow = rx_lane(j, F);
+				first_slow = rx_lane(ch.j, F);
 			l.flags |= GCL_TCPO_STOPPED;
 		}
-		if (valid) {
+		if (ch.valid) {
 			const bool fast = lane < F;
-			k.verdict[j] = (uint8_t)(fast ? GCL_TCPRX_FAST : GCL_TCPRX_SLOW);
-			k.sflags[j] = (uint8_t)sf_mine;
-			k.after[j] = after_mine;
-			k.copy_len[j] = (uint16_t)(fast ? len : 0);
-			k.dst_off[j] = fast ? (uint32_t)(seq - cn.rcv_nxt) : 0; /* layout adds conn_off[c] */
+			k.verdict[ch.j] = (uint8_t)(fast ? GCL_TCPRX_FAST : GCL_TCPRX_SLOW);
+			k.sflags[ch.j] = (uint8_t)sf_mine;
+			k.after[ch.j] = after_mine;
+			k.copy_len[ch.j] = (uint16_t)(fast ? len : 0);
+			k.dst_off[ch.j] = fast ? (uint32_t)(seq - cn.rcv_nxt) : 0; /* layout adds conn_off[c] */
 		}
 	}
 	if (lane == 0) {
-		k.out_conn[3 * (size_t)c] = make_uint4(l.snd_una, l.snd_wnd, l.snd_wl1, l.snd_wl2);
-		k.out_conn[3 * (size_t)c + 1] = make_uint4(l.rcv_nxt, l.rcv_wnd, nfast, nslow);
-		k.out_conn[3 * (size_t)c + 2] = make_uint4(nacks, first_slow, (l.cnt & 0xFFu) | (l.flags & 0xFFu) << 8, 0);
+		rx_conn_store(k, c, l, nfast, nslow, nacks, first_slow);
 		k.wakes[c] = wakes;
 	}
 }
 
 /* ---- layout ---- */
 
+/*
+ * The entries that have bytes to copy get their connection's offset.  Which
+ * those are is the call's: gcl_tcp_rx keys on the verdict FAST, the three
+ * later calls (@kByCopyLen) on copy_len != 0.  A FAST segment of length 0
+ * tells them apart, so the key is no run-time choice.
+ */
+template <bool kByCopyLen>
 __global__ void __launch_bounds__(kRxThreads) rx_fix_kernel(RxParams k)
 {
 	for (uint64_t j = (uint64_t)blockIdx.x * kRxThreads + threadIdx.x; j < k.m;
 	     j += (uint64_t)gridDim.x * kRxThreads) {
 		const uint32_t c = k.cookie[j];
-		if (c < k.nconn && k.verdict[j] == GCL_TCPRX_FAST)
+		if (c < k.nconn && (kByCopyLen ? k.copy_len[j] != 0 : k.verdict[j] == GCL_TCPRX_FAST))
 			k.dst_off[j] += k.conn_off[c];
-	}
-}
-
-/* FAST, SLOW, BYTES, ACKS and WAKES of the call, summed over the connections */
-__global__ void __launch_bounds__(kRxThreads) rx_counts_kernel(RxParams k)
-{
-	__shared__ unsigned long long blk[5];
-	unsigned long long v[5] = {0, 0, 0, 0, 0};
-
-	if (threadIdx.x < 5)
-		blk[threadIdx.x] = 0;
-	__syncthreads();
-	for (uint32_t c = blockIdx.x * kRxThreads + threadIdx.x; c < k.nconn; c += gridDim.x * kRxThreads) {
-		const uint4 o1 = k.out_conn[3 * (size_t)c + 1], o2 = k.out_conn[3 * (size_t)c + 2];
-		v[0] += o1.z;
-		v[1] += o1.w;
-		v[2] += (uint32_t)(o1.x - k.conn[3 * (size_t)c + 1].y);
-		v[3] += o2.x;
-		v[4] += k.wakes[c];
-	}
-#pragma unroll
-	for (int x = 0; x < 5; x++) {
-		for (int d = 32; d; d >>= 1) {
-			const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v[x], d);
-			const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v[x] >> 32), d);
-			v[x] += (unsigned long long)hi << 32 | lo;
-		}
-		if ((threadIdx.x & 63) == 0 && v[x])
-			atomicAdd(&blk[x], v[x]);
-	}
-	__syncthreads();
-	if (threadIdx.x < 5 && blk[threadIdx.x]) {
-		const uint32_t slot[5] = {GCL_TCPRXC_FAST, GCL_TCPRXC_SLOW, GCL_TCPRXC_BYTES, GCL_TCPRXC_ACKS,
-		                          GCL_TCPRXC_WAKES};
-		atomicAdd(k.counts + slot[threadIdx.x], blk[threadIdx.x]);
 	}
 }
 
@@ -611,6 +636,70 @@ __device__ __forceinline__ uint32_t rx_pop(bool b)
 	return (uint32_t)__popcll(__ballot(b));
 }
 
+/* the live words a serial walk carries for connection c */
+__device__ __forceinline__ struct gcl_tcprxf_live rxf_live_of(const RxfParams &p, const struct gcl_tcp_conn &cn,
+                                                              uint32_t c)
+{
+	struct gcl_tcprxf_live x;
+
+	x.l = gcl_tcprx_live_of(&cn);
+	x.rep_acks = p.rep_acks ? p.rep_acks[c] : 0;
+	x.fast_rtx_ack = 0;
+	x.xflags = 0;
+	return x;
+}
+
+/* the segment of lane @at of a chunk: wave-uniform */
+__device__ __forceinline__ struct gcl_tcprx_seg rx_seg_at(const uint4 &rec, uint32_t at)
+{
+	const uint32_t z = rx_lane(rec.z, at);
+	const struct gcl_tcprx_seg s = {rx_lane(rec.x, at), rx_lane(rec.y, at), z & 0xFFFFu, rx_lane(rec.w, at), z >> 16};
+
+	return s;
+}
+
+/* what a serial walk counts per connection; wave-uniform */
+struct RxfTally {
+	uint32_t nfast, nslow, first_slow;
+	uint32_t nacks, wakes, nrule2, ndropped, ntxw, nfrtx, ndup;
+};
+
+/*
+ * The end of a chunk of which the first H segments went through: the counts,
+ * the stop, and the sflags' tallies as ballots (lanes at and past H hold 0).
+ */
+__device__ __forceinline__ void rxf_chunk_end(RxfTally &t, struct gcl_tcprx_live &l, const RxChunk &ch, uint32_t H,
+                                              bool stopped, uint32_t sf_mine)
+{
+	t.nfast += H;
+	t.nslow += ch.nv - H;
+	if (H < ch.nv) {
+		if (!stopped)
+			t.first_slow = rx_lane(ch.j, H);
+		l.flags |= GCL_TCPO_STOPPED;
+	}
+	if (H) {
+		t.nacks += rx_pop(sf_mine & GCL_TCPRX_SF_ACK_NOW);
+		t.wakes += rx_pop(sf_mine & GCL_TCPRX_SF_WAKE);
+		t.nrule2 += rx_pop(sf_mine & GCL_TCPRX_SF_RULE2);
+		t.ndropped += rx_pop(sf_mine & GCL_TCPRX_SF_DROPPED);
+		t.ntxw += rx_pop(sf_mine & GCL_TCPRX_SF_TXWAKE);
+		t.nfrtx += rx_pop(sf_mine & GCL_TCPRX_SF_FASTRTX);
+		t.ndup += rx_pop(sf_mine & GCL_TCPRXF_EV_DUPACK);
+	}
+}
+
+/* connection c's out_conn, out_ext, xcnt (its fourth word is the queue walk's OOO count) and WAKE count; one
+ * lane calls it */
+__device__ __forceinline__ void rxf_conn_store(const RxfParams &p, uint32_t c, const struct gcl_tcprxf_live &x,
+                                               const RxfTally &t, uint32_t nooo)
+{
+	rx_conn_store(p.k, c, x.l, t.nfast, t.nslow, t.nacks, t.first_slow);
+	p.out_ext[c] = make_uint4(t.nrule2, t.ndropped, x.fast_rtx_ack, (x.rep_acks & 0xFFu) | (x.xflags & 0xFFu) << 8);
+	p.xcnt[c] = make_uint4(t.ntxw, t.nfrtx, t.ndup, nooo);
+	p.k.wakes[c] = t.wakes;
+}
+
 /*
  * One wave per connection, as rx_walk_kernel.  An unaccepted segment does not
  * move rcv_nxt, so the stop is no prefix sum: the wave walks the chunk's
@@ -622,45 +711,25 @@ __global__ void __launch_bounds__(kRxThreads) rxf_walk_kernel(RxfParams p, const
 {
 	const RxParams &k = p.k;
 	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRxWaves + (threadIdx.x >> 6)));
+	const uint32_t c = rx_wave_conn();
 
 	if (c >= k.nconn)
 		return;
-	struct gcl_tcp_conn cn;
-	{
-		const uint4 a = k.conn[3 * (size_t)c], b = k.conn[3 * (size_t)c + 1], d = k.conn[3 * (size_t)c + 2];
-		cn.snd_una = a.x; cn.snd_nxt = a.y; cn.snd_wnd = a.z; cn.snd_wl1 = a.w;
-		cn.snd_wl2 = b.x; cn.rcv_nxt = b.y; cn.rcv_wnd = b.z;
-		cn.rcv_mss = (uint16_t)b.w; cn.snd_wscale = (uint8_t)(b.w >> 16); cn.flags = (uint8_t)(b.w >> 24);
-		cn.acks_delayed_cnt = (uint8_t)d.x;
-	}
-	struct gcl_tcprxf_live x;
-	x.l = gcl_tcprx_live_of(&cn);
-	x.rep_acks = p.rep_acks ? p.rep_acks[c] : 0;
-	x.fast_rtx_ack = 0;
-	x.xflags = 0;
-	const uint2 rn = k.run[c];
-	const uint64_t re = rn.y < k.m ? rn.y : k.m;
-	const uint64_t rs = rn.x < re ? rn.x : re;
-	uint32_t nfast = 0, nslow = 0, nacks = 0, wakes = 0, first_slow = GCL_TCPRX_NONE;
-	uint32_t nrule2 = 0, ndropped = 0, ntxw = 0, nfrtx = 0, ndup = 0;
+	const struct gcl_tcp_conn cn = rx_conn_load(k, c);
+	struct gcl_tcprxf_live x = rxf_live_of(p, cn, c);
+	uint64_t rs, re;
+	rx_run_bounds(k, c, &rs, &re);
+	RxfTally t = {0, 0, GCL_TCPRX_NONE, 0, 0, 0, 0, 0, 0, 0};
 
 	for (uint64_t base = rs; base < re; base += 64) { /* uniform */
-		const uint32_t nv = re - base < 64 ? (uint32_t)(re - base) : 64;
-		const bool valid = lane < nv;
-		uint32_t j = valid ? sorted[base + lane] : 0;
-		if (j >= k.m)
-			j = (uint32_t)(k.m - 1);
-		const uint4 rec = valid ? k.rec[j] : make_uint4(0, 0, 0, 0);
+		const RxChunk ch = rx_gather(k, sorted, base, re, lane);
 		const bool stopped = (x.l.flags & GCL_TCPO_STOPPED) != 0;
 		uint32_t H = 0, sf_mine = 0, after_mine = 0, copy_mine = 0;
 
 		if (!stopped) {
-			H = nv;
-			for (uint32_t at = 0; at < nv; at++) { /* uniform */
-				const uint32_t z = rx_lane(rec.z, at);
-				const struct gcl_tcprx_seg s = {rx_lane(rec.x, at), rx_lane(rec.y, at), z & 0xFFFFu,
-				                                rx_lane(rec.w, at), z >> 16};
+			H = ch.nv;
+			for (uint32_t at = 0; at < ch.nv; at++) { /* uniform */
+				const struct gcl_tcprx_seg s = rx_seg_at(ch.rec, at);
 				uint32_t sf, cp;
 				if (gcl_tcprxf_one(&cn, &x, &s, &sf, &cp) != GCL_TCPRX_FAST) {
 					H = at;
@@ -673,92 +742,17 @@ __global__ void __launch_bounds__(kRxThreads) rxf_walk_kernel(RxfParams p, const
 				}
 			}
 		}
-		nfast += H;
-		nslow += nv - H;
-		if (H < nv) {
-			if (!stopped)
-				first_slow = rx_lane(j, H);
-			x.l.flags |= GCL_TCPO_STOPPED;
-		}
-		if (H) { /* lanes at and past H hold 0 */
-			nacks += rx_pop(sf_mine & GCL_TCPRX_SF_ACK_NOW);
-			wakes += rx_pop(sf_mine & GCL_TCPRX_SF_WAKE);
-			nrule2 += rx_pop(sf_mine & GCL_TCPRX_SF_RULE2);
-			ndropped += rx_pop(sf_mine & GCL_TCPRX_SF_DROPPED);
-			ntxw += rx_pop(sf_mine & GCL_TCPRX_SF_TXWAKE);
-			nfrtx += rx_pop(sf_mine & GCL_TCPRX_SF_FASTRTX);
-			ndup += rx_pop(sf_mine & GCL_TCPRXF_EV_DUPACK);
-		}
-		if (valid) {
-			k.verdict[j] = (uint8_t)(lane < H ? GCL_TCPRX_FAST : GCL_TCPRX_SLOW);
-			k.sflags[j] = (uint8_t)sf_mine;
-			k.after[j] = after_mine;
-			k.copy_len[j] = (uint16_t)copy_mine;
-			k.dst_off[j] = copy_mine ? (uint32_t)(rec.x - cn.rcv_nxt) : 0; /* layout adds conn_off[c] */
+		rxf_chunk_end(t, x.l, ch, H, stopped, sf_mine);
+		if (ch.valid) {
+			k.verdict[ch.j] = (uint8_t)(lane < H ? GCL_TCPRX_FAST : GCL_TCPRX_SLOW);
+			k.sflags[ch.j] = (uint8_t)sf_mine;
+			k.after[ch.j] = after_mine;
+			k.copy_len[ch.j] = (uint16_t)copy_mine;
+			k.dst_off[ch.j] = copy_mine ? (uint32_t)(ch.rec.x - cn.rcv_nxt) : 0; /* layout adds conn_off[c] */
 		}
 	}
-	if (lane == 0) {
-		k.out_conn[3 * (size_t)c] = make_uint4(x.l.snd_una, x.l.snd_wnd, x.l.snd_wl1, x.l.snd_wl2);
-		k.out_conn[3 * (size_t)c + 1] = make_uint4(x.l.rcv_nxt, x.l.rcv_wnd, nfast, nslow);
-		k.out_conn[3 * (size_t)c + 2] = make_uint4(nacks, first_slow, (x.l.cnt & 0xFFu) | (x.l.flags & 0xFFu) << 8, 0);
-		p.out_ext[c] = make_uint4(nrule2, ndropped, x.fast_rtx_ack, (x.rep_acks & 0xFFu) | (x.xflags & 0xFFu) << 8);
-		p.xcnt[c] = make_uint4(ntxw, nfrtx, ndup, 0);
-		k.wakes[c] = wakes;
-	}
-}
-
-__global__ void __launch_bounds__(kRxThreads) rxf_fix_kernel(RxParams k)
-{
-	for (uint64_t j = (uint64_t)blockIdx.x * kRxThreads + threadIdx.x; j < k.m;
-	     j += (uint64_t)gridDim.x * kRxThreads) {
-		const uint32_t c = k.cookie[j];
-		if (c < k.nconn && k.copy_len[j])
-			k.dst_off[j] += k.conn_off[c];
-	}
-}
-
-/* the ten counters of the call that the walk decides, summed over the connections */
-__global__ void __launch_bounds__(kRxThreads) rxf_counts_kernel(RxfParams p)
-{
-	constexpr int N = 10;
-	const RxParams &k = p.k;
-	__shared__ unsigned long long blk[N];
-	unsigned long long v[N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-	if (threadIdx.x < N)
-		blk[threadIdx.x] = 0;
-	__syncthreads();
-	for (uint32_t c = blockIdx.x * kRxThreads + threadIdx.x; c < k.nconn; c += gridDim.x * kRxThreads) {
-		const uint4 o1 = k.out_conn[3 * (size_t)c + 1], o2 = k.out_conn[3 * (size_t)c + 2];
-		const uint4 e = p.out_ext[c], xc = p.xcnt[c];
-		v[0] += o1.z;
-		v[1] += o1.w;
-		v[2] += (uint32_t)(o1.x - k.conn[3 * (size_t)c + 1].y);
-		v[3] += o2.x;
-		v[4] += k.wakes[c];
-		v[5] += e.x;
-		v[6] += xc.x;
-		v[7] += xc.y;
-		v[8] += xc.z;
-		v[9] += e.y;
-	}
-#pragma unroll
-	for (int x = 0; x < N; x++) {
-		for (int d = 32; d; d >>= 1) {
-			const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v[x], d);
-			const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v[x] >> 32), d);
-			v[x] += (unsigned long long)hi << 32 | lo;
-		}
-		if ((threadIdx.x & 63) == 0 && v[x])
-			atomicAdd(&blk[x], v[x]);
-	}
-	__syncthreads();
-	if (threadIdx.x < N && blk[threadIdx.x]) {
-		const uint32_t slot[N] = {GCL_TCPRXC_FAST, GCL_TCPRXC_SLOW, GCL_TCPRXC_BYTES, GCL_TCPRXC_ACKS,
-		                          GCL_TCPRXC_WAKES, GCL_TCPRXFC_RULE2, GCL_TCPRXFC_TXWAKES, GCL_TCPRXFC_FASTRTX,
-		                          GCL_TCPRXFC_DUPACKS, GCL_TCPRXFC_DROPPED};
-		atomicAdd(k.counts + slot[threadIdx.x], blk[threadIdx.x]);
-	}
+	if (lane == 0)
+		rxf_conn_store(p, c, x, t, 0);
 }
 
 /* ---- gcl_tcp_rx_ooo: its walk with the queue in the wave, the output queues and its counters ---- */
@@ -814,6 +808,19 @@ __device__ __forceinline__ void rxo_range(const RxoParams &p, uint32_t c, uint32
 	}
 }
 
+/* what gcl_tcp_rx_states adds to gcl_tcp_rx_ooo's walk; every other launch is gcl_tcp_rx_ooo's */
+struct RxsParams {
+	RxoParams o;
+	const uint8_t *state;   /* [nconn] or NULL */
+	uint8_t *ev;            /* [m] */
+	uint32_t *rst_seq;      /* [m] */
+	uint8_t *state_after;   /* [m] */
+	uint8_t *state_out;     /* [nconn] */
+};
+
+__device__ __forceinline__ const RxoParams &rxo_base(const RxoParams &p) { return p; }
+__device__ __forceinline__ const RxoParams &rxo_base(const RxsParams &p) { return p.o; }
+
 /* a live queue entry, entry i in lane i: @fl is flags | src << 16, @idx the index into q or the list */
 struct RxoEnt {
 	uint32_t seq, end, fl, idx;
@@ -826,6 +833,27 @@ __device__ __forceinline__ uint32_t rxo_find(const RxoEnt &e, uint32_t qn, uint3
 	const uint64_t ends = __ballot((t & GCL_TCPRXO_POS_END) != 0), seqs = __ballot((t & GCL_TCPRXO_POS_SEQ) != 0);
 
 	return gcl_tcprxo_pos(ends, seqs);
+}
+
+/* the insert: the lanes at and above @pos move up by one (the caller has seen to qn < 64), lane @pos takes @n */
+__device__ __forceinline__ void rxo_insert(RxoEnt &e, uint32_t lane, uint32_t pos, const RxoEnt &n)
+{
+	const RxoEnt u = {(uint32_t)__shfl_up((int)e.seq, 1), (uint32_t)__shfl_up((int)e.end, 1),
+	                  (uint32_t)__shfl_up((int)e.fl, 1), (uint32_t)__shfl_up((int)e.idx, 1)};
+
+	if (lane > pos)
+		e = u;
+	if (lane == pos)
+		e = n;
+}
+
+/* the pop of the head: every lane takes the entry above it */
+__device__ __forceinline__ void rxo_pop(RxoEnt &e)
+{
+	e.seq = (uint32_t)__shfl_down((int)e.seq, 1);
+	e.end = (uint32_t)__shfl_down((int)e.end, 1);
+	e.fl = (uint32_t)__shfl_down((int)e.fl, 1);
+	e.idx = (uint32_t)__shfl_down((int)e.idx, 1);
 }
 
 /* what an entry that leaves the queue gets; one lane calls it, and nothing else stores these words */
@@ -848,27 +876,68 @@ __device__ __forceinline__ void rxo_fate(const RxoParams &p, uint32_t fl, uint32
 	}
 }
 
+/* a segment's locals that outlive the text step: the rule's own struct, and its gcl_tcprxo_mid part */
+__device__ __forceinline__ struct gcl_tcprxo_mid &rxo_mid(struct gcl_tcprxo_mid &mid) { return mid; }
+__device__ __forceinline__ struct gcl_tcprxo_mid &rxo_mid(struct gcl_tcprxs_mid &mid) { return mid.o; }
+
 /*
+ * The queue walk of gcl_tcp_rx_ooo (P = RxoParams, the rule of gcl_tcprxo.h)
+ * and of gcl_tcp_rx_states (P = RxsParams, the rule of gcl_tcprxs.h, @S below).
+ *
  * One wave per connection, serial and wave-uniform over each chunk as
  * rxf_walk_kernel, with the connection's out-of-order queue in the wave's
  * registers: entry i in lane i, @qn entries.  The insert position is two
  * ballots, an insert or a pop a one-lane shift, the drain reads lane 0.
+ * Wave-uniform throughout: qn, st, dead, H, the counters and the live words.
+ *
+ * What differs between the two calls, all of it under `if constexpr (S)`:
+ *   taking      _ooo takes a connection whose flags gcl_tcprxo_state_ok accepts
+ *               and whose input queue fits; a ballot un-takes one whose input
+ *               queue holds a FIN entry, and a taken one gets ELIGIBLE into
+ *               cn.flags.  _states takes by gcl_tcprxs_state_ok of the live
+ *               state @st (gcl_tcprxs_state_of, made uniform), FIN entries
+ *               included, and leaves cn.flags alone.
+ *   full queue  whether a segment's insert would be the 65th: _ooo asks
+ *               gcl_tcprxo_reaches_ooo; _states runs gcl_tcprxs_head on copies
+ *               of the live words and the state, so that a stop leaves them
+ *               untouched, then gcl_tcprxo_in_order.  A known cost: while a
+ *               queue holds 64 entries every segment runs that head twice.
+ *   head        gcl_tcprxo_head may say STOP; gcl_tcprxs_head carries @st and
+ *               never does, but after a FAIL or a PUT (@dead) the next
+ *               segment stops.
+ *   text        the end is seq + len, for _states seq + mid.slen (the FIN's
+ *               octet); the in-order wake is each rule's own; _states' append
+ *               takes the FIN bit, in order the segment's and in the drain the
+ *               popped entry's (its flags word at lane 0), notes it in
+ *               mid.fin, and gcl_tcprxs_fin follows gcl_tcprxo_text_tail.
+ *   segment     _states only: dead, the four event counters, and ev, rst_seq
+ *               and state_after of the entry.
+ *   the end     _states only: state_out[c], and the four counters added to
+ *               counts by lane 0: atomics that only add.
  *
  * Store order.  copy_len, dst_off, oflags and skip of a list entry that was
  * QUEUED are stored exactly once, when its fate is known: by rxo_fate when it
  * is popped (in this chunk or a later one) or at the end of the walk when it
  * is HELD; the chunk's own store skips such an entry.  The same holds for the
- * qin_* words of an input entry.  So no two stores of this kernel hit one
- * address and no fence is needed.
+ * qin_* words of an input entry.  ev, rst_seq and state_after of an entry are
+ * final when the entry has been processed and only the chunk's own store
+ * writes them.  So no two stores of this kernel hit one address and no fence
+ * is needed.
  */
-__global__ void __launch_bounds__(kRxThreads) rxo_walk_kernel(RxoParams p, const uint32_t *sorted)
+template <typename P>
+__global__ void __launch_bounds__(kRxThreads) rxq_walk_kernel(P ps, const uint32_t *sorted)
 {
+	constexpr bool S = std::is_same<P, RxsParams>::value;
+	typedef typename std::conditional<S, struct gcl_tcprxs_mid, struct gcl_tcprxo_mid>::type Mid;
+	const RxoParams &p = rxo_base(ps);
 	const RxParams &k = p.f.k;
 	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRxWaves + (threadIdx.x >> 6)));
+	const uint32_t c = rx_wave_conn();
 
 	if (c >= k.nconn)
 		return;
+	/* rx_conn_load's unpack, in place: through the helper the _states instantiation, which spills
+	 * SGPRs to VGPR lanes as it is, comes out with 36 B of scratch per lane that it never touches */
 	struct gcl_tcp_conn cn;
 	{
 		const uint4 a = k.conn[3 * (size_t)c], b = k.conn[3 * (size_t)c + 1], d = k.conn[3 * (size_t)c + 2];
@@ -877,16 +946,15 @@ __global__ void __launch_bounds__(kRxThreads) rxo_walk_kernel(RxoParams p, const
 		cn.rcv_mss = (uint16_t)b.w; cn.snd_wscale = (uint8_t)(b.w >> 16); cn.flags = (uint8_t)(b.w >> 24);
 		cn.acks_delayed_cnt = (uint8_t)d.x;
 	}
-	struct gcl_tcprxf_live x;
-	x.l = gcl_tcprx_live_of(&cn);
-	x.rep_acks = p.f.rep_acks ? p.f.rep_acks[c] : 0;
-	x.fast_rtx_ack = 0;
-	x.xflags = 0;
+	struct gcl_tcprxf_live x = rxf_live_of(p.f, cn, c);
+	uint32_t st = 0;
+	if constexpr (S)
+		st = (uint32_t)__builtin_amdgcn_readfirstlane((int)gcl_tcprxs_state_of(ps.state, c, cn.flags));
 	const uint32_t rcv0 = cn.rcv_nxt;
 	uint32_t qs, qe;
 	rxo_range(p, c, &qs, &qe);
 	const uint32_t nin = qe - qs;
-	bool taken = gcl_tcprxo_state_ok(cn.flags) && nin <= GCL_TCPOOO_CAP;
+	bool taken = (S ? gcl_tcprxs_state_ok(st) : gcl_tcprxo_state_ok(cn.flags)) && nin <= GCL_TCPOOO_CAP;
 	RxoEnt e = {0, 0, 0, 0};
 	if (taken && lane < nin) {
 		const uint4 w = p.q[qs + lane];
@@ -895,81 +963,97 @@ __global__ void __launch_bounds__(kRxThreads) rxo_walk_kernel(RxoParams p, const
 		e.fl = w.w & 0xFFFFu;
 		e.idx = qs + lane;
 	}
-	if (__ballot(taken && lane < nin && (e.fl & GCL_TCPRX_FIN)))
-		taken = false;
+	if constexpr (!S) {
+		if (__ballot(taken && lane < nin && (e.fl & GCL_TCPRX_FIN)))
+			taken = false;
+		if (taken)
+			cn.flags |= GCL_TCPC_ELIGIBLE;
+	}
 	uint32_t qn = taken ? nin : 0;
-	if (taken)
-		cn.flags |= GCL_TCPC_ELIGIBLE;
-	else if (nin)
+	if (!taken && nin)
 		x.xflags |= GCL_TCPX_QSKIP;
 
-	const uint2 rn = k.run[c];
-	const uint64_t re = rn.y < k.m ? rn.y : k.m;
-	const uint64_t rs = rn.x < re ? rn.x : re;
-	uint32_t nfast = 0, nslow = 0, nacks = 0, wakes = 0, first_slow = GCL_TCPRX_NONE;
-	uint32_t nrule2 = 0, ndropped = 0, ntxw = 0, nfrtx = 0, ndup = 0;
+	uint64_t rs, re;
+	rx_run_bounds(k, c, &rs, &re);
+	RxfTally t = {0, 0, GCL_TCPRX_NONE, 0, 0, 0, 0, 0, 0, 0};
 	uint32_t nooo = 0, nqueued = 0, ndrained = 0, nfreed = 0, nhead = 0;
+	uint32_t nrst = 0, nfail = 0, nfin = 0, nstate = 0;
+	bool dead = false; /* _states: a FAIL or a PUT went by: the next segment stops */
 
 	for (uint64_t base = rs; base < re; base += 64) { /* uniform */
-		const uint32_t nv = re - base < 64 ? (uint32_t)(re - base) : 64;
-		const bool valid = lane < nv;
-		uint32_t j = valid ? sorted[base + lane] : 0;
-		if (j >= k.m)
-			j = (uint32_t)(k.m - 1);
-		const uint4 rec = valid ? k.rec[j] : make_uint4(0, 0, 0, 0);
+		const RxChunk ch = rx_gather(k, sorted, base, re, lane);
 		const bool stopped = (x.l.flags & GCL_TCPO_STOPPED) != 0;
 		uint32_t H = 0, sf_mine = 0, after_mine = 0, copy_mine = 0, head_mine = 0, of_mine = 0, rel_mine = 0;
+		uint32_t ev_mine = 0, rseq_mine = 0, st_mine = 0;
 
 		if (!stopped && taken) {
-			H = nv;
-			for (uint32_t at = 0; at < nv; at++) { /* uniform */
-				const uint32_t z = rx_lane(rec.z, at);
-				const struct gcl_tcprx_seg s = {rx_lane(rec.x, at), rx_lane(rec.y, at), z & 0xFFFFu,
-				                                rx_lane(rec.w, at), z >> 16};
-				const uint32_t jj = rx_lane(j, at);
+			H = ch.nv;
+			for (uint32_t at = 0; at < ch.nv; at++) { /* uniform */
+				const struct gcl_tcprx_seg s = rx_seg_at(ch.rec, at);
+				const uint32_t jj = rx_lane(ch.j, at);
 				const uint32_t rel = x.l.rcv_nxt - rcv0; /* where an in-order piece lands */
-				struct gcl_tcprxo_mid mid;
+				Mid mid;
 				uint32_t sf = 0, len = 0, head = 0, of = 0;
-				bool stop = false;
+				bool stop = S && dead;
 
-				if (qn == GCL_TCPOOO_CAP && gcl_tcprxo_reaches_ooo(&cn, &x.l, &s))
-					stop = rxo_find(e, qn, lane, s.seq, s.seq + s.len) != GCL_TCPRXO_REJECT;
+				if constexpr (S) {
+					mid.ev = 0;
+					mid.rst_seq = 0;
+					if (!stop && qn == GCL_TCPOOO_CAP) { /* asked on copies: nothing moves */
+						struct gcl_tcprxf_live xt = x;
+						uint32_t stt = st, lt;
+
+						if (gcl_tcprxs_head(&cn, &xt, &stt, &s, qn, &mid, &lt) == GCL_TCPRXO_TEXT &&
+						    !gcl_tcprxo_in_order(&xt.l, s.seq))
+							stop = rxo_find(e, qn, lane, s.seq, s.seq + mid.slen) != GCL_TCPRXO_REJECT;
+					}
+				} else {
+					if (qn == GCL_TCPOOO_CAP && gcl_tcprxo_reaches_ooo(&cn, &x.l, &s))
+						stop = rxo_find(e, qn, lane, s.seq, s.seq + s.len) != GCL_TCPRXO_REJECT;
+				}
 				if (!stop) {
-					const uint32_t st = gcl_tcprxo_head(&cn, &x, &s, qn, &mid, &len);
+					uint32_t t0;
 
-					if (st == GCL_TCPRXO_STOP) {
+					if constexpr (S)
+						t0 = gcl_tcprxs_head(&cn, &x, &st, &s, qn, &mid, &len);
+					else
+						t0 = gcl_tcprxo_head(&cn, &x, &s, qn, &mid, &len);
+					if (!S && t0 == GCL_TCPRXO_STOP) {
 						stop = true;
-					} else if (st == GCL_TCPRXO_FASTED) {
-						sf = mid.sf;
+					} else if (t0 == GCL_TCPRXO_FASTED) {
+						sf = rxo_mid(mid).sf;
 					} else {
-						if (st == GCL_TCPRXO_TEXT) {
+						if (t0 == GCL_TCPRXO_TEXT) {
+							uint32_t end = s.seq + s.len;
 							int used = 1, wake = 0;
 
+							if constexpr (S)
+								end = s.seq + mid.slen;
 							if (gcl_tcprxo_in_order(&x.l, s.seq)) {
-								wake = gcl_tcprxo_in_order_wake(&x.l, s.flags);
-								gcl_tcprxo_append(&x.l, s.seq, s.seq + s.len, &head, &len);
+								if constexpr (S) {
+									wake = gcl_tcprxs_in_order_wake(&x.l, s.flags);
+									if (wake && (s.flags & GCL_TCPRX_FIN))
+										mid.fin = 1;
+									gcl_tcprxs_append(&x.l, s.seq, end, (s.flags & GCL_TCPRX_FIN) != 0, &head, &len);
+								} else {
+									wake = gcl_tcprxo_in_order_wake(&x.l, s.flags);
+									gcl_tcprxo_append(&x.l, s.seq, end, &head, &len);
+								}
 								if (head) {
 									of |= GCL_OOOF_HEADCLIP;
 									nhead++;
 								}
 							} else {
-								const uint32_t pos = rxo_find(e, qn, lane, s.seq, s.seq + s.len);
+								const uint32_t pos = rxo_find(e, qn, lane, s.seq, end);
 
 								of |= GCL_OOOF_OOO;
 								nooo++;
 								if (pos == GCL_TCPRXO_REJECT) {
 									used = 0;
-								} else { /* the lanes at and above pos move up by one */
-									const RxoEnt u = {(uint32_t)__shfl_up((int)e.seq, 1), (uint32_t)__shfl_up((int)e.end, 1),
-									                  (uint32_t)__shfl_up((int)e.fl, 1), (uint32_t)__shfl_up((int)e.idx, 1)};
-									if (lane > pos)
-										e = u;
-									if (lane == pos) {
-										e.seq = s.seq;
-										e.end = s.seq + s.len;
-										e.fl = s.flags | 1u << 16;
-										e.idx = jj;
-									}
+								} else {
+									const RxoEnt n = {s.seq, end, s.flags | 1u << 16, jj};
+
+									rxo_insert(e, lane, pos, n);
 									qn++;
 									of |= GCL_OOOF_QUEUED;
 									nqueued++;
@@ -978,36 +1062,48 @@ __global__ void __launch_bounds__(kRxThreads) rxo_walk_kernel(RxoParams p, const
 							while (used && qn) { /* uniform: the drain reads lane 0 */
 								const uint32_t hs = rx_lane(e.seq, 0), he = rx_lane(e.end, 0);
 								const uint32_t hf = rx_lane(e.fl, 0), hi = rx_lane(e.idx, 0);
-								const uint32_t t = gcl_tcprxo_drain_test(hs, he, x.l.rcv_nxt);
+								const uint32_t dt = gcl_tcprxo_drain_test(hs, he, x.l.rcv_nxt);
 								const uint32_t r = x.l.rcv_nxt - rcv0;
 								uint32_t h = 0, ln = 0;
 
-								if (t == GCL_TCPRXO_BREAK)
+								if (dt == GCL_TCPRXO_BREAK)
 									break;
-								if (t == GCL_TCPRXO_APPEND) {
+								if (dt == GCL_TCPRXO_APPEND) {
 									wake = 1;
-									gcl_tcprxo_append(&x.l, hs, he, &h, &ln);
+									if constexpr (S) {
+										if (hf & GCL_TCPRX_FIN)
+											mid.fin = 1;
+										gcl_tcprxs_append(&x.l, hs, he, (hf & GCL_TCPRX_FIN) != 0, &h, &ln);
+									} else {
+										gcl_tcprxo_append(&x.l, hs, he, &h, &ln);
+									}
 									nhead += h != 0;
 									ndrained++;
 								} else {
 									nfreed++;
 								}
 								if (lane == 0)
-									rxo_fate(p, hf, hi, t, h, ln, r);
-								e.seq = (uint32_t)__shfl_down((int)e.seq, 1);
-								e.end = (uint32_t)__shfl_down((int)e.end, 1);
-								e.fl = (uint32_t)__shfl_down((int)e.fl, 1);
-								e.idx = (uint32_t)__shfl_down((int)e.idx, 1);
+									rxo_fate(p, hf, hi, dt, h, ln, r);
+								rxo_pop(e);
 								qn--;
 							}
-							gcl_tcprxo_text_tail(&x.l, &mid, used, wake, qn);
+							gcl_tcprxo_text_tail(&x.l, &rxo_mid(mid), used, wake, qn);
+							if constexpr (S)
+								gcl_tcprxs_fin(&x, &st, &mid);
 						}
-						sf = gcl_tcprxo_done(&x.l, &mid);
+						sf = gcl_tcprxo_done(&x.l, &rxo_mid(mid));
 					}
 				}
 				if (stop) {
 					H = at;
 					break;
+				}
+				if constexpr (S) {
+					dead = gcl_tcprxs_ends(mid.ev);
+					nrst += (mid.ev & (GCL_TCPS_RST | GCL_TCPS_RST_ACK)) != 0;
+					nfail += (mid.ev & GCL_TCPS_FAIL) != 0;
+					nfin += (mid.ev & GCL_TCPS_FIN) != 0;
+					nstate += (mid.ev & GCL_TCPS_STATE) != 0;
 				}
 				if (lane == at) {
 					sf_mine = sf;
@@ -1016,34 +1112,29 @@ __global__ void __launch_bounds__(kRxThreads) rxo_walk_kernel(RxoParams p, const
 					head_mine = head;
 					of_mine = of;
 					rel_mine = rel;
+					if constexpr (S) {
+						ev_mine = mid.ev;
+						rseq_mine = mid.rst_seq;
+						st_mine = st;
+					}
 				}
 			}
 		}
-		nfast += H;
-		nslow += nv - H;
-		if (H < nv) {
-			if (!stopped)
-				first_slow = rx_lane(j, H);
-			x.l.flags |= GCL_TCPO_STOPPED;
-		}
-		if (H) { /* lanes at and past H hold 0 */
-			nacks += rx_pop(sf_mine & GCL_TCPRX_SF_ACK_NOW);
-			wakes += rx_pop(sf_mine & GCL_TCPRX_SF_WAKE);
-			nrule2 += rx_pop(sf_mine & GCL_TCPRX_SF_RULE2);
-			ndropped += rx_pop(sf_mine & GCL_TCPRX_SF_DROPPED);
-			ntxw += rx_pop(sf_mine & GCL_TCPRX_SF_TXWAKE);
-			nfrtx += rx_pop(sf_mine & GCL_TCPRX_SF_FASTRTX);
-			ndup += rx_pop(sf_mine & GCL_TCPRXF_EV_DUPACK);
-		}
-		if (valid) {
-			k.verdict[j] = (uint8_t)(lane < H ? GCL_TCPRX_FAST : GCL_TCPRX_SLOW);
-			k.sflags[j] = (uint8_t)sf_mine;
-			k.after[j] = after_mine;
+		rxf_chunk_end(t, x.l, ch, H, stopped, sf_mine);
+		if (ch.valid) {
+			k.verdict[ch.j] = (uint8_t)(lane < H ? GCL_TCPRX_FAST : GCL_TCPRX_SLOW);
+			k.sflags[ch.j] = (uint8_t)sf_mine;
+			k.after[ch.j] = after_mine;
+			if constexpr (S) {
+				ps.ev[ch.j] = (uint8_t)ev_mine;
+				ps.rst_seq[ch.j] = rseq_mine;
+				ps.state_after[ch.j] = (uint8_t)st_mine;
+			}
 			if (!(of_mine & GCL_OOOF_QUEUED)) { /* a queued entry gets these with its fate */
-				k.copy_len[j] = (uint16_t)copy_mine;
-				k.dst_off[j] = copy_mine ? rel_mine : 0; /* layout adds conn_off[c] */
-				p.oflags[j] = (uint8_t)of_mine;
-				p.skip[j] = (uint16_t)head_mine;
+				k.copy_len[ch.j] = (uint16_t)copy_mine;
+				k.dst_off[ch.j] = copy_mine ? rel_mine : 0; /* layout adds conn_off[c] */
+				p.oflags[ch.j] = (uint8_t)of_mine;
+				p.skip[ch.j] = (uint16_t)head_mine;
 			}
 		}
 	}
@@ -1070,295 +1161,22 @@ __global__ void __launch_bounds__(kRxThreads) rxo_walk_kernel(RxoParams p, const
 	}
 	const uint32_t nheld = (uint32_t)__popcll(heldmask);
 	if (lane == 0) {
-		k.out_conn[3 * (size_t)c] = make_uint4(x.l.snd_una, x.l.snd_wnd, x.l.snd_wl1, x.l.snd_wl2);
-		k.out_conn[3 * (size_t)c + 1] = make_uint4(x.l.rcv_nxt, x.l.rcv_wnd, nfast, nslow);
-		k.out_conn[3 * (size_t)c + 2] = make_uint4(nacks, first_slow, (x.l.cnt & 0xFFu) | (x.l.flags & 0xFFu) << 8, 0);
-		p.f.out_ext[c] = make_uint4(nrule2, ndropped, x.fast_rtx_ack, (x.rep_acks & 0xFFu) | (x.xflags & 0xFFu) << 8);
-		p.f.xcnt[c] = make_uint4(ntxw, nfrtx, ndup, nooo);
+		rxf_conn_store(p.f, c, x, t, nooo);
 		p.ocnt[c] = make_uint4(nqueued, ndrained, nfreed, nhead);
 		p.qmeta[c] = make_uint4(qn | (uint32_t)staged << 8 | (uint32_t)taken << 9, nheld, (uint32_t)heldmask,
 		                        (uint32_t)(heldmask >> 32));
-		k.wakes[c] = wakes;
-	}
-}
-
-/* ---- gcl_tcp_rx_states: gcl_tcp_rx_ooo's walk with the live state; every other launch is gcl_tcp_rx_ooo's ---- */
-
-struct RxsParams {
-	RxoParams o;
-	const uint8_t *state;   /* [nconn] or NULL */
-	uint8_t *ev;            /* [m] */
-	uint32_t *rst_seq;      /* [m] */
-	uint8_t *state_after;   /* [m] */
-	uint8_t *state_out;     /* [nconn] */
-};
-
-/*
- * rxo_walk_kernel with one more wave-uniform register, the live state @st, and
- * the rule of gcl_tcprxs.h: one wave per connection, serial and wave-uniform
- * over each 64-segment chunk, the queue in the lanes.  The FIN of a popped
- * entry is its flags word at lane 0.  Whether a segment's insert would be the
- * 65th is asked on copies of the live words, so a stop leaves them untouched.
- * A known cost: while a connection's queue holds 64 entries every one of its
- * segments runs gcl_tcprxs_head twice, once on the copies and once for real.
- *
- * Store order is rxo_walk_kernel's: copy_len, dst_off, oflags and skip of a
- * QUEUED entry are stored once, with its fate.  ev, rst_seq and state_after of
- * an entry are final when the entry has been processed and only the chunk's
- * own store writes them.  No two stores of this kernel hit one address and no
- * fence is needed.  The four counters this call adds are summed per connection
- * here and added to counts by lane 0: atomics that only add.
- */
-__global__ void __launch_bounds__(kRxThreads) rxs_walk_kernel(RxsParams ps, const uint32_t *sorted)
-{
-	const RxoParams &p = ps.o;
-	const RxParams &k = p.f.k;
-	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRxWaves + (threadIdx.x >> 6)));
-
-	if (c >= k.nconn)
-		return;
-	struct gcl_tcp_conn cn;
-	{
-		const uint4 a = k.conn[3 * (size_t)c], b = k.conn[3 * (size_t)c + 1], d = k.conn[3 * (size_t)c + 2];
-		cn.snd_una = a.x; cn.snd_nxt = a.y; cn.snd_wnd = a.z; cn.snd_wl1 = a.w;
-		cn.snd_wl2 = b.x; cn.rcv_nxt = b.y; cn.rcv_wnd = b.z;
-		cn.rcv_mss = (uint16_t)b.w; cn.snd_wscale = (uint8_t)(b.w >> 16); cn.flags = (uint8_t)(b.w >> 24);
-		cn.acks_delayed_cnt = (uint8_t)d.x;
-	}
-	struct gcl_tcprxf_live x;
-	x.l = gcl_tcprx_live_of(&cn);
-	x.rep_acks = p.f.rep_acks ? p.f.rep_acks[c] : 0;
-	x.fast_rtx_ack = 0;
-	x.xflags = 0;
-	uint32_t st = (uint32_t)__builtin_amdgcn_readfirstlane((int)gcl_tcprxs_state_of(ps.state, c, cn.flags));
-	const uint32_t rcv0 = cn.rcv_nxt;
-	uint32_t qs, qe;
-	rxo_range(p, c, &qs, &qe);
-	const uint32_t nin = qe - qs;
-	const bool taken = gcl_tcprxs_state_ok(st) && nin <= GCL_TCPOOO_CAP;
-	RxoEnt e = {0, 0, 0, 0};
-	if (taken && lane < nin) {
-		const uint4 w = p.q[qs + lane];
-		e.seq = w.x;
-		e.end = w.y;
-		e.fl = w.w & 0xFFFFu;
-		e.idx = qs + lane;
-	}
-	uint32_t qn = taken ? nin : 0;
-	if (!taken && nin)
-		x.xflags |= GCL_TCPX_QSKIP;
-
-	const uint2 rn = k.run[c];
-	const uint64_t re = rn.y < k.m ? rn.y : k.m;
-	const uint64_t rs = rn.x < re ? rn.x : re;
-	uint32_t nfast = 0, nslow = 0, nacks = 0, wakes = 0, first_slow = GCL_TCPRX_NONE;
-	uint32_t nrule2 = 0, ndropped = 0, ntxw = 0, nfrtx = 0, ndup = 0;
-	uint32_t nooo = 0, nqueued = 0, ndrained = 0, nfreed = 0, nhead = 0;
-	uint32_t nrst = 0, nfail = 0, nfin = 0, nstate = 0;
-	bool dead = false; /* a FAIL or a PUT went by: the next segment stops */
-
-	for (uint64_t base = rs; base < re; base += 64) { /* uniform */
-		const uint32_t nv = re - base < 64 ? (uint32_t)(re - base) : 64;
-		const bool valid = lane < nv;
-		uint32_t j = valid ? sorted[base + lane] : 0;
-		if (j >= k.m)
-			j = (uint32_t)(k.m - 1);
-		const uint4 rec = valid ? k.rec[j] : make_uint4(0, 0, 0, 0);
-		const bool stopped = (x.l.flags & GCL_TCPO_STOPPED) != 0;
-		uint32_t H = 0, sf_mine = 0, after_mine = 0, copy_mine = 0, head_mine = 0, of_mine = 0, rel_mine = 0;
-		uint32_t ev_mine = 0, rseq_mine = 0, st_mine = 0;
-
-		if (!stopped && taken) {
-			H = nv;
-			for (uint32_t at = 0; at < nv; at++) { /* uniform */
-				const uint32_t z = rx_lane(rec.z, at);
-				const struct gcl_tcprx_seg s = {rx_lane(rec.x, at), rx_lane(rec.y, at), z & 0xFFFFu,
-				                                rx_lane(rec.w, at), z >> 16};
-				const uint32_t jj = rx_lane(j, at);
-				const uint32_t rel = x.l.rcv_nxt - rcv0; /* where an in-order piece lands */
-				struct gcl_tcprxs_mid mid;
-				uint32_t sf = 0, len = 0, head = 0, of = 0;
-				bool stop = dead;
-
-				mid.ev = 0;
-				mid.rst_seq = 0;
-				if (!stop && qn == GCL_TCPOOO_CAP) { /* would it be the 65th insert?  asked on copies: nothing moves */
-					struct gcl_tcprxf_live xt = x;
-					uint32_t stt = st, lt;
-
-					if (gcl_tcprxs_head(&cn, &xt, &stt, &s, qn, &mid, &lt) == GCL_TCPRXO_TEXT &&
-					    !gcl_tcprxo_in_order(&xt.l, s.seq))
-						stop = rxo_find(e, qn, lane, s.seq, s.seq + mid.slen) != GCL_TCPRXO_REJECT;
-				}
-				if (!stop) {
-					const uint32_t t0 = gcl_tcprxs_head(&cn, &x, &st, &s, qn, &mid, &len);
-
-					if (t0 == GCL_TCPRXO_FASTED) {
-						sf = mid.o.sf;
-					} else {
-						if (t0 == GCL_TCPRXO_TEXT) {
-							const uint32_t end = s.seq + mid.slen;
-							int used = 1, wake = 0;
-
-							if (gcl_tcprxo_in_order(&x.l, s.seq)) {
-								wake = gcl_tcprxs_in_order_wake(&x.l, s.flags);
-								if (wake && (s.flags & GCL_TCPRX_FIN))
-									mid.fin = 1;
-								gcl_tcprxs_append(&x.l, s.seq, end, (s.flags & GCL_TCPRX_FIN) != 0, &head, &len);
-								if (head) {
-									of |= GCL_OOOF_HEADCLIP;
-									nhead++;
-								}
-							} else {
-								const uint32_t pos = rxo_find(e, qn, lane, s.seq, end);
-
-								of |= GCL_OOOF_OOO;
-								nooo++;
-								if (pos == GCL_TCPRXO_REJECT) {
-									used = 0;
-								} else { /* the lanes at and above pos move up by one; qn < 64 here */
-									const RxoEnt u = {(uint32_t)__shfl_up((int)e.seq, 1), (uint32_t)__shfl_up((int)e.end, 1),
-									                  (uint32_t)__shfl_up((int)e.fl, 1), (uint32_t)__shfl_up((int)e.idx, 1)};
-									if (lane > pos)
-										e = u;
-									if (lane == pos) {
-										e.seq = s.seq;
-										e.end = end;
-										e.fl = s.flags | 1u << 16;
-										e.idx = jj;
-									}
-									qn++;
-									of |= GCL_OOOF_QUEUED;
-									nqueued++;
-								}
-							}
-							while (used && qn) { /* uniform: the drain reads lane 0 */
-								const uint32_t hs = rx_lane(e.seq, 0), he = rx_lane(e.end, 0);
-								const uint32_t hf = rx_lane(e.fl, 0), hi = rx_lane(e.idx, 0);
-								const uint32_t t = gcl_tcprxo_drain_test(hs, he, x.l.rcv_nxt);
-								const uint32_t r = x.l.rcv_nxt - rcv0;
-								uint32_t h = 0, ln = 0;
-
-								if (t == GCL_TCPRXO_BREAK)
-									break;
-								if (t == GCL_TCPRXO_APPEND) {
-									wake = 1;
-									if (hf & GCL_TCPRX_FIN)
-										mid.fin = 1;
-									gcl_tcprxs_append(&x.l, hs, he, (hf & GCL_TCPRX_FIN) != 0, &h, &ln);
-									nhead += h != 0;
-									ndrained++;
-								} else {
-									nfreed++;
-								}
-								if (lane == 0)
-									rxo_fate(p, hf, hi, t, h, ln, r);
-								e.seq = (uint32_t)__shfl_down((int)e.seq, 1);
-								e.end = (uint32_t)__shfl_down((int)e.end, 1);
-								e.fl = (uint32_t)__shfl_down((int)e.fl, 1);
-								e.idx = (uint32_t)__shfl_down((int)e.idx, 1);
-								qn--;
-							}
-							gcl_tcprxo_text_tail(&x.l, &mid.o, used, wake, qn);
-							gcl_tcprxs_fin(&x, &st, &mid);
-						}
-						sf = gcl_tcprxo_done(&x.l, &mid.o);
-					}
-				}
-				if (stop) {
-					H = at;
-					break;
-				}
-				dead = gcl_tcprxs_ends(mid.ev);
-				nrst += (mid.ev & (GCL_TCPS_RST | GCL_TCPS_RST_ACK)) != 0;
-				nfail += (mid.ev & GCL_TCPS_FAIL) != 0;
-				nfin += (mid.ev & GCL_TCPS_FIN) != 0;
-				nstate += (mid.ev & GCL_TCPS_STATE) != 0;
-				if (lane == at) {
-					sf_mine = sf;
-					after_mine = x.l.rcv_nxt;
-					copy_mine = len;
-					head_mine = head;
-					of_mine = of;
-					rel_mine = rel;
-					ev_mine = mid.ev;
-					rseq_mine = mid.rst_seq;
-					st_mine = st;
-				}
+		if constexpr (S) {
+			ps.state_out[c] = (uint8_t)st;
+			if (k.counts) {
+				if (nrst)
+					atomicAdd(k.counts + GCL_TCPRXSC_RSTS, (unsigned long long)nrst);
+				if (nfail)
+					atomicAdd(k.counts + GCL_TCPRXSC_FAILS, (unsigned long long)nfail);
+				if (nfin)
+					atomicAdd(k.counts + GCL_TCPRXSC_FINS, (unsigned long long)nfin);
+				if (nstate)
+					atomicAdd(k.counts + GCL_TCPRXSC_STATE_CHANGES, (unsigned long long)nstate);
 			}
-		}
-		nfast += H;
-		nslow += nv - H;
-		if (H < nv) {
-			if (!stopped)
-				first_slow = rx_lane(j, H);
-			x.l.flags |= GCL_TCPO_STOPPED;
-		}
-		if (H) { /* lanes at and past H hold 0 */
-			nacks += rx_pop(sf_mine & GCL_TCPRX_SF_ACK_NOW);
-			wakes += rx_pop(sf_mine & GCL_TCPRX_SF_WAKE);
-			nrule2 += rx_pop(sf_mine & GCL_TCPRX_SF_RULE2);
-			ndropped += rx_pop(sf_mine & GCL_TCPRX_SF_DROPPED);
-			ntxw += rx_pop(sf_mine & GCL_TCPRX_SF_TXWAKE);
-			nfrtx += rx_pop(sf_mine & GCL_TCPRX_SF_FASTRTX);
-			ndup += rx_pop(sf_mine & GCL_TCPRXF_EV_DUPACK);
-		}
-		if (valid) {
-			k.verdict[j] = (uint8_t)(lane < H ? GCL_TCPRX_FAST : GCL_TCPRX_SLOW);
-			k.sflags[j] = (uint8_t)sf_mine;
-			k.after[j] = after_mine;
-			ps.ev[j] = (uint8_t)ev_mine;
-			ps.rst_seq[j] = rseq_mine;
-			ps.state_after[j] = (uint8_t)st_mine;
-			if (!(of_mine & GCL_OOOF_QUEUED)) { /* a queued entry gets these with its fate */
-				k.copy_len[j] = (uint16_t)copy_mine;
-				k.dst_off[j] = copy_mine ? rel_mine : 0; /* layout adds conn_off[c] */
-				p.oflags[j] = (uint8_t)of_mine;
-				p.skip[j] = (uint16_t)head_mine;
-			}
-		}
-	}
-	/* the queue as it stands: HELD and KEPT, and the entries staged for rxo_qout_kernel */
-	const bool staged = rs < re;
-	const bool mine = lane < qn, held = mine && (e.fl >> 16) != 0;
-	const uint64_t heldmask = __ballot(held);
-	const uint32_t rank_l = (uint32_t)__popcll(heldmask & ((1ull << lane) - 1)), rank_q = lane - rank_l;
-	if (mine) {
-		uint32_t ref = e.idx;
-		if (held) {
-			k.copy_len[e.idx] = 0;
-			k.dst_off[e.idx] = 0;
-			p.oflags[e.idx] = GCL_OOOF_OOO | GCL_OOOF_QUEUED | GCL_OOOF_HELD;
-			p.skip[e.idx] = 0;
-		} else {
-			p.qin_state[e.idx] = GCL_OOOQ_KEPT;
-			ref = p.q[e.idx].z;
-		}
-		if (staged) /* rank_q < qe - qs and rank_l < re - rs: below nq, and below nq + m */
-			p.stage[held ? (size_t)p.nq + rs + rank_l : (size_t)qs + rank_q] = make_uint4(e.seq, e.end, ref, e.fl);
-	}
-	const uint32_t nheld = (uint32_t)__popcll(heldmask);
-	if (lane == 0) {
-		k.out_conn[3 * (size_t)c] = make_uint4(x.l.snd_una, x.l.snd_wnd, x.l.snd_wl1, x.l.snd_wl2);
-		k.out_conn[3 * (size_t)c + 1] = make_uint4(x.l.rcv_nxt, x.l.rcv_wnd, nfast, nslow);
-		k.out_conn[3 * (size_t)c + 2] = make_uint4(nacks, first_slow, (x.l.cnt & 0xFFu) | (x.l.flags & 0xFFu) << 8, 0);
-		p.f.out_ext[c] = make_uint4(nrule2, ndropped, x.fast_rtx_ack, (x.rep_acks & 0xFFu) | (x.xflags & 0xFFu) << 8);
-		p.f.xcnt[c] = make_uint4(ntxw, nfrtx, ndup, nooo);
-		p.ocnt[c] = make_uint4(nqueued, ndrained, nfreed, nhead);
-		p.qmeta[c] = make_uint4(qn | (uint32_t)staged << 8 | (uint32_t)taken << 9, nheld, (uint32_t)heldmask,
-		                        (uint32_t)(heldmask >> 32));
-		k.wakes[c] = wakes;
-		ps.state_out[c] = (uint8_t)st;
-		if (k.counts) {
-			if (nrst)
-				atomicAdd(k.counts + GCL_TCPRXSC_RSTS, (unsigned long long)nrst);
-			if (nfail)
-				atomicAdd(k.counts + GCL_TCPRXSC_FAILS, (unsigned long long)nfail);
-			if (nfin)
-				atomicAdd(k.counts + GCL_TCPRXSC_FINS, (unsigned long long)nfin);
-			if (nstate)
-				atomicAdd(k.counts + GCL_TCPRXSC_STATE_CHANGES, (unsigned long long)nstate);
 		}
 	}
 }
@@ -1381,9 +1199,8 @@ __global__ void __launch_bounds__(kRxThreads) rxo_qout_kernel(RxoParams p)
 	const uint64_t heldmask = (uint64_t)meta.w << 32 | meta.z;
 	const bool held = (heldmask >> lane & 1) != 0;
 	const uint32_t rank_l = (uint32_t)__popcll(heldmask & ((1ull << lane) - 1)), rank_q = lane - rank_l;
-	const uint2 rn = k.run[c];
-	const uint64_t re = rn.y < k.m ? rn.y : k.m;
-	const uint64_t rs = rn.x < re ? rn.x : re;
+	uint64_t rs, re;
+	rx_run_bounds(k, c, &rs, &re);
 	uint32_t qs, qe;
 	rxo_range(p, c, &qs, &qe);
 
@@ -1407,37 +1224,65 @@ __global__ void __launch_bounds__(kRxThreads) rxo_qout_kernel(RxoParams p)
 	}
 }
 
-/* the sixteen counters of the call that the walk decides, summed over the connections */
-__global__ void __launch_bounds__(kRxThreads) rxo_counts_kernel(RxoParams p)
+/* ---- the counters the walk decides, summed over the connections ---- */
+
+__device__ __forceinline__ const RxParams &rx_base(const RxParams &k) { return k; }
+__device__ __forceinline__ const RxParams &rx_base(const RxfParams &p) { return p.k; }
+__device__ __forceinline__ const RxParams &rx_base(const RxoParams &p) { return p.f.k; }
+
+/* connection c's share of a call's counters, in the order of rx_counts_kernel's slot table: gcl_tcp_rx's 5 */
+__device__ __forceinline__ void rx_counts_of(const RxParams &k, uint32_t c, unsigned long long *v)
 {
-	constexpr int N = 16;
-	const RxParams &k = p.f.k;
+	const uint4 o1 = k.out_conn[3 * (size_t)c + 1], o2 = k.out_conn[3 * (size_t)c + 2];
+
+	v[0] += o1.z;
+	v[1] += o1.w;
+	v[2] += (uint32_t)(o1.x - k.conn[3 * (size_t)c + 1].y);
+	v[3] += o2.x;
+	v[4] += k.wakes[c];
+}
+
+/* gcl_tcp_rx_full's 10: those 5 and its own */
+__device__ __forceinline__ void rx_counts_of(const RxfParams &p, uint32_t c, unsigned long long *v)
+{
+	const uint4 e = p.out_ext[c], xc = p.xcnt[c];
+
+	rx_counts_of(p.k, c, v);
+	v[5] += e.x;
+	v[6] += xc.x;
+	v[7] += xc.y;
+	v[8] += xc.z;
+	v[9] += e.y;
+}
+
+/* gcl_tcp_rx_ooo's and gcl_tcp_rx_states' 16: those 10 and the queue's */
+__device__ __forceinline__ void rx_counts_of(const RxoParams &p, uint32_t c, unsigned long long *v)
+{
+	const uint4 oc = p.ocnt[c];
+
+	rx_counts_of(p.f, c, v);
+	v[10] += p.f.xcnt[c].w;
+	v[11] += oc.x;
+	v[12] += oc.y;
+	v[13] += oc.z;
+	v[14] += oc.w;
+	v[15] += p.qmeta[c].y;
+}
+
+/* N counters: a lane's sum over its connections, the wave's by shuffles, the block's in LDS, one add per
+ * counter per block */
+template <int N, typename P>
+__global__ void __launch_bounds__(kRxThreads) rx_counts_kernel(P p)
+{
+	const RxParams &k = rx_base(p);
 	__shared__ unsigned long long blk[N];
-	unsigned long long v[N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	unsigned long long v[N] = {};
 
 	if (threadIdx.x < N)
 		blk[threadIdx.x] = 0;
 	__syncthreads();
-	for (uint32_t c = blockIdx.x * kRxThreads + threadIdx.x; c < k.nconn; c += gridDim.x * kRxThreads) {
-		const uint4 o1 = k.out_conn[3 * (size_t)c + 1], o2 = k.out_conn[3 * (size_t)c + 2];
-		const uint4 ex = p.f.out_ext[c], xc = p.f.xcnt[c], oc = p.ocnt[c];
-		v[0] += o1.z;
-		v[1] += o1.w;
-		v[2] += (uint32_t)(o1.x - k.conn[3 * (size_t)c + 1].y);
-		v[3] += o2.x;
-		v[4] += k.wakes[c];
-		v[5] += ex.x;
-		v[6] += xc.x;
-		v[7] += xc.y;
-		v[8] += xc.z;
-		v[9] += ex.y;
-		v[10] += xc.w;
-		v[11] += oc.x;
-		v[12] += oc.y;
-		v[13] += oc.z;
-		v[14] += oc.w;
-		v[15] += p.qmeta[c].y;
-	}
+	for (uint32_t c = blockIdx.x * kRxThreads + threadIdx.x; c < k.nconn; c += gridDim.x * kRxThreads)
+		rx_counts_of(p, c, v);
 #pragma unroll
 	for (int x = 0; x < N; x++) {
 		for (int d = 32; d; d >>= 1) {
@@ -1450,10 +1295,10 @@ __global__ void __launch_bounds__(kRxThreads) rxo_counts_kernel(RxoParams p)
 	}
 	__syncthreads();
 	if (threadIdx.x < N && blk[threadIdx.x]) {
-		const uint32_t slot[N] = {GCL_TCPRXC_FAST, GCL_TCPRXC_SLOW, GCL_TCPRXC_BYTES, GCL_TCPRXC_ACKS,
-		                          GCL_TCPRXC_WAKES, GCL_TCPRXFC_RULE2, GCL_TCPRXFC_TXWAKES, GCL_TCPRXFC_FASTRTX,
-		                          GCL_TCPRXFC_DUPACKS, GCL_TCPRXFC_DROPPED, GCL_TCPRXOC_OOO, GCL_TCPRXOC_QUEUED,
-		                          GCL_TCPRXOC_DRAINED, GCL_TCPRXOC_FREED, GCL_TCPRXOC_HEADCLIP, GCL_TCPRXOC_HELD};
+		const uint32_t slot[16] = {GCL_TCPRXC_FAST, GCL_TCPRXC_SLOW, GCL_TCPRXC_BYTES, GCL_TCPRXC_ACKS,
+		                           GCL_TCPRXC_WAKES, GCL_TCPRXFC_RULE2, GCL_TCPRXFC_TXWAKES, GCL_TCPRXFC_FASTRTX,
+		                           GCL_TCPRXFC_DUPACKS, GCL_TCPRXFC_DROPPED, GCL_TCPRXOC_OOO, GCL_TCPRXOC_QUEUED,
+		                           GCL_TCPRXOC_DRAINED, GCL_TCPRXOC_FREED, GCL_TCPRXOC_HEADCLIP, GCL_TCPRXOC_HELD};
 		atomicAdd(k.counts + slot[threadIdx.x], blk[threadIdx.x]);
 	}
 }
@@ -1557,13 +1402,33 @@ static size_t rxo_extra(uint64_t m, uint32_t nconn, uint32_t nq)
 	return 32 * (size_t)nconn + rx_up16(4 * (((size_t)nconn + kRxChunk - 1) / kRxChunk)) + 16 * ((size_t)nq + m);
 }
 
+/* the three launches of the exclusive scan of io.load(0 .. total) */
+template <typename Io>
+static void rx_scan(const Io &io, uint32_t total, typename Io::T *csum, hipStream_t s)
+{
+	const uint32_t nchunks = (total + kRxChunk - 1) / kRxChunk;
+
+	hipLaunchKernelGGL(rx_scan_sum_kernel<Io>, dim3(nchunks), dim3(kRxThreads), 0, s, io, total, csum);
+	hipLaunchKernelGGL(rx_scan_top_kernel<Io>, dim3(1), dim3(kRxTopThreads), 0, s, io, csum, nchunks);
+	hipLaunchKernelGGL(rx_scan_apply_kernel<Io>, dim3(nchunks), dim3(kRxThreads), 0, s, io, total, csum);
+}
+
+/*
+ * The driver of the four calls.  @full, @ooo and @sts nest: each call passes
+ * what it adds to the one before it and NULL for the rest.  Validation, the
+ * parameter blocks, the geometry, parse, group, runs and the three scans are
+ * the same code for all four; a call chooses its walk, its fix-up key, whether
+ * the queues are written out, and how many counters are summed.
+ */
 static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprx_in *in,
-                  const struct gcl_tcprx_out *out, const RxFull *full, const RxOoo *ooo, uint64_t *counts,
-                  void *workspace, size_t workspace_bytes, void *hip_stream)
+                  const struct gcl_tcprx_out *out, const RxFull *full, const RxOoo *ooo, const RxStates *sts,
+                  uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
 	hipStream_t s = (hipStream_t)hip_stream;
 	RxGeom g;
 
+	if (sts && (!full || !ooo || !ooo->in))
+		return -EINVAL;
 	if (!c || !b || !in || !out || in->size != sizeof(*in) || !gcl_pay_align_ok(in->align) ||
 	    (!in->order && in->m != b->n) || rx_geometry(in->m, in->nconn, in->blocks, &g) || !in->sock ||
 	    !out->conn_off)
@@ -1590,6 +1455,13 @@ static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl
 		if (rx_misaligned(oi->q_off, 4) || rx_misaligned(oi->q, 16) || rx_misaligned(oo->skip, 2) ||
 		    rx_misaligned(oo->qin_skip, 2) || rx_misaligned(oo->qin_len, 2) || rx_misaligned(oo->qin_dst_off, 8) ||
 		    rx_misaligned(oo->qout_off, 4) || rx_misaligned(oo->qout, 16) || rx_misaligned(oo->totals, 8))
+			return -EINVAL;
+	}
+	if (sts) {
+		const struct gcl_tcprxs_out *so = sts->out;
+
+		if (!so || (in->m && (!so->ev || !so->rst_seq || !so->state_after)) ||
+		    (in->nconn && !so->state_out) || rx_misaligned(so->rst_seq, 4))
 			return -EINVAL;
 	}
 	/* gcl_tcp_rx_full keeps xcnt behind gcl_tcp_rx's workspace, gcl_tcp_rx_ooo its own behind that */
@@ -1663,6 +1535,14 @@ static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl
 		                       hipMemsetAsync(oo->totals, 0, 8, s) != hipSuccess))
 			return -EIO;
 	}
+	if (sts && in->m) { /* NA, NOCONN and DROP entries, and with nconn == 0 every entry */
+		const struct gcl_tcprxs_out *so = sts->out;
+
+		if (hipMemsetAsync(so->ev, 0, in->m, s) != hipSuccess ||
+		    hipMemsetAsync(so->rst_seq, 0, 4 * (size_t)in->m, s) != hipSuccess ||
+		    hipMemsetAsync(so->state_after, 0, in->m, s) != hipSuccess)
+			return -EIO;
+	}
 	if (in->nconn == 0) { /* every TCP segment is NOCONN: nothing to group, walk or lay out */
 		if (in->m)
 			hipLaunchKernelGGL(rx_parse_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
@@ -1677,15 +1557,9 @@ static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl
 		hipLaunchKernelGGL(rx_parse_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
 		for (uint32_t p = 0; p < g.passes; p++) {
 			const RxPass ps = {p ? k.idx[0] : nullptr, k.idx[p], p * kRxDigitBits, g.nb[p], g.kbits[p]};
-			const RxHistIo io = {k.hist, k.tot};
-			const uint32_t total = ps.nb * k.ranges;
-			const uint32_t nchunks = (total + kRxChunk - 1) / kRxChunk;
 			const dim3 grid((k.ranges + kRxWaves - 1) / kRxWaves);
 			hipLaunchKernelGGL(rx_count_kernel, grid, dim3(kRxThreads), 0, s, k, ps);
-			hipLaunchKernelGGL(rx_scan_sum_kernel<RxHistIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, total, k.csum);
-			hipLaunchKernelGGL(rx_scan_top_kernel<RxHistIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, k.csum, nchunks);
-			hipLaunchKernelGGL(rx_scan_apply_kernel<RxHistIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, total,
-			                   k.csum);
+			rx_scan(RxHistIo{k.hist, k.tot}, ps.nb * k.ranges, k.csum, s);
 			hipLaunchKernelGGL(rx_scatter_kernel, grid, dim3(kRxThreads), 0, s, k, ps);
 		}
 		hipLaunchKernelGGL(rx_runs_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k, sorted);
@@ -1724,263 +1598,34 @@ static int rx_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl
 		ko.qsum = (uint32_t *)at;
 		at += rx_up16(4 * (((size_t)in->nconn + kRxChunk - 1) / kRxChunk));
 		ko.stage = (uint4 *)at;
-		hipLaunchKernelGGL(rxo_walk_kernel, wgrid, dim3(kRxThreads), 0, s, ko, sorted);
-		const RxQoutIo io = {ko.qmeta, ko.qout_off, ko.totals, in->nconn};
-		const uint32_t nchunks = (in->nconn + kRxChunk - 1) / kRxChunk;
-		hipLaunchKernelGGL(rx_scan_sum_kernel<RxQoutIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn, ko.qsum);
-		hipLaunchKernelGGL(rx_scan_top_kernel<RxQoutIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, ko.qsum, nchunks);
-		hipLaunchKernelGGL(rx_scan_apply_kernel<RxQoutIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn,
-		                   ko.qsum);
-	} else if (full) {
-		hipLaunchKernelGGL(rxf_walk_kernel, dim3((in->nconn + kRxWaves - 1) / kRxWaves), dim3(kRxThreads), 0, s,
-		                   kf, sorted);
-	} else {
-		hipLaunchKernelGGL(rx_walk_kernel, dim3((in->nconn + kRxWaves - 1) / kRxWaves), dim3(kRxThreads), 0, s, k,
-		                   sorted);
-	}
-	{
-		const RxConnIo io = {k.conn, k.out_conn, k.conn_off, in->nconn, k.amask};
-		const uint32_t nchunks = (in->nconn + kRxChunk - 1) / kRxChunk;
-		hipLaunchKernelGGL(rx_scan_sum_kernel<RxConnIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn, k.lsum);
-		hipLaunchKernelGGL(rx_scan_top_kernel<RxConnIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, k.lsum, nchunks);
-		hipLaunchKernelGGL(rx_scan_apply_kernel<RxConnIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn,
-		                   k.lsum);
-	}
-	const dim3 cgrid(std::min<uint32_t>((in->nconn + kRxThreads - 1) / kRxThreads, cus * 2));
-	if (ooo) {
-		if (in->m)
-			hipLaunchKernelGGL(rxf_fix_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
-		hipLaunchKernelGGL(rxo_qout_kernel, wgrid, dim3(kRxThreads), 0, s, ko);
-		if (counts)
-			hipLaunchKernelGGL(rxo_counts_kernel, cgrid, dim3(kRxThreads), 0, s, ko);
-	} else if (full) {
-		if (in->m)
-			hipLaunchKernelGGL(rxf_fix_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
-		if (counts)
-			hipLaunchKernelGGL(rxf_counts_kernel, cgrid, dim3(kRxThreads), 0, s, kf);
-	} else {
-		if (in->m)
-			hipLaunchKernelGGL(rx_fix_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
-		if (counts)
-			hipLaunchKernelGGL(rx_counts_kernel, cgrid, dim3(kRxThreads), 0, s, k);
-	}
-	return hipGetLastError() == hipSuccess ? 0 : -EIO;
-}
-
-/*
- * gcl_tcp_rx_states' own driver: rx_run as gcl_tcp_rx_ooo takes it, with the
- * three arrays of @sts cleared and rxs_walk_kernel in rxo_walk_kernel's place.
- * rx_run itself, which the three older calls share, is left as it was.
- */
-static int rxs_run(struct gcl_ctx *c, const struct gcl_batch *b, const struct gcl_tcprx_in *in,
-                  const struct gcl_tcprx_out *out, const RxFull *full, const RxOoo *ooo, const RxStates *sts,
-                  uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-	hipStream_t s = (hipStream_t)hip_stream;
-	RxGeom g;
-
-	if (!full || !ooo || !sts || !ooo->in)
-		return -EINVAL;
-	if (!c || !b || !in || !out || in->size != sizeof(*in) || !gcl_pay_align_ok(in->align) ||
-	    (!in->order && in->m != b->n) || rx_geometry(in->m, in->nconn, in->blocks, &g) || !in->sock ||
-	    !out->conn_off)
-		return -EINVAL;
-	if (in->nconn && (!in->conn || !out->out_conn || !full->out_ext))
-		return -EINVAL;
-	if (rx_misaligned(full->out_ext, 16))
-		return -EINVAL;
-	if (in->m && (!out->verdict || !out->sflags || !out->rcv_nxt_after || !out->copy_len || !out->dst_off))
-		return -EINVAL;
-	if (rx_misaligned(in->order, 4) || rx_misaligned(in->sock, 4) || rx_misaligned(in->conn, 16) ||
-	    rx_misaligned(out->rcv_nxt_after, 4) || rx_misaligned(out->copy_len, 2) ||
-	    rx_misaligned(out->dst_off, 8) || rx_misaligned(out->out_conn, 16) ||
-	    rx_misaligned(out->conn_off, 8) || rx_misaligned(counts, 8))
-		return -EINVAL;
-	{
-		const struct gcl_tcprxo_in *oi = ooo->in;
-		const struct gcl_tcprxo_out *oo = ooo->out;
-
-		if (!oo || oi->nq > (1u << 31) || !oo->qout_off || !oo->totals || (in->m && (!oo->oflags || !oo->skip)) ||
-		    (oi->nq && (!oi->q || !oo->qin_state || !oo->qin_skip || !oo->qin_len || !oo->qin_dst_off)) ||
-		    (oi->q_out_cap && !oo->qout))
-			return -EINVAL;
-		if (rx_misaligned(oi->q_off, 4) || rx_misaligned(oi->q, 16) || rx_misaligned(oo->skip, 2) ||
-		    rx_misaligned(oo->qin_skip, 2) || rx_misaligned(oo->qin_len, 2) || rx_misaligned(oo->qin_dst_off, 8) ||
-		    rx_misaligned(oo->qout_off, 4) || rx_misaligned(oo->qout, 16) || rx_misaligned(oo->totals, 8))
-			return -EINVAL;
-	}
-	{
-		const struct gcl_tcprxs_out *so = sts->out;
-
-		if (!so || (in->m && (!so->ev || !so->rst_seq || !so->state_after)) ||
-		    (in->nconn && !so->state_out) || rx_misaligned(so->rst_seq, 4))
-			return -EINVAL;
-	}
-	/* gcl_tcp_rx_full keeps xcnt behind gcl_tcp_rx's workspace, gcl_tcp_rx_ooo its own behind that */
-	const size_t xbytes = 16 * (size_t)in->nconn + rxo_extra(in->m, in->nconn, ooo->in->nq);
-	if (!workspace || rx_misaligned(workspace, 16) || workspace_bytes < g.bytes + xbytes)
-		return -EINVAL;
-	if (in->m && (!b->frames || b->frames_len == UINT64_MAX || b->n > (1ull << 40) ||
-	              (!b->offs && (b->stride < 16 || (b->stride & 15) || b->stride > (1u << 20))) ||
-	              !b->pkt_len || rx_misaligned(b->pkt_len, 2)))
-		return -EINVAL;
-	if (hipSetDevice(c->device) != hipSuccess)
-		return -EIO;
-	c->last_stream = s;
-
-	uint8_t *ws = (uint8_t *)workspace;
-	RxParams k;
-	k.frames = b->frames;
-	k.frames_len = b->frames_len;
-	k.stride = b->stride;
-	k.offs = b->offs;
-	k.pkt_len = b->pkt_len;
-	k.n = b->n;
-	k.order = in->order;
-	k.sock = in->sock;
-	k.l4_status = in->l4_status;
-	k.conn = (const uint4 *)in->conn;
-	k.verdict = out->verdict;
-	k.sflags = out->sflags;
-	k.after = out->rcv_nxt_after;
-	k.copy_len = out->copy_len;
-	k.dst_off = out->dst_off;
-	k.out_conn = (uint4 *)out->out_conn;
-	k.conn_off = (unsigned long long *)out->conn_off;
-	k.counts = (unsigned long long *)counts;
-	k.rec = (uint4 *)(ws + g.rec);
-	k.cookie = (uint32_t *)(ws + g.cookie);
-	k.idx[0] = (uint32_t *)(ws + g.idx[0]);
-	k.idx[1] = (uint32_t *)(ws + g.idx[1]);
-	k.hist = (uint32_t *)(ws + g.hist);
-	k.csum = (uint32_t *)(ws + g.csum);
-	k.lsum = (unsigned long long *)(ws + g.lsum);
-	k.tot = (uint32_t *)(ws + g.tot);
-	k.run = (uint2 *)(ws + g.run);
-	k.wakes = (uint32_t *)(ws + g.wakes);
-	k.m = in->m;
-	k.nconn = in->nconn;
-	k.amask = in->align ? in->align - 1 : 0;
-
-	const uint32_t cus = (uint32_t)(c->num_cus > 0 ? c->num_cus : 1);
-	const uint64_t tiles = (in->m + kRxThreads - 1) / kRxThreads;
-	const unsigned egrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)cus * 8));
-	k.ranges = in->blocks ? in->blocks :
-	           (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(tiles, std::min<uint32_t>(cus * kRxBlocksPerCu,
-	                                                                                      GCL_TCPRX_MAX_BLOCKS)));
-	k.range_len = (uint32_t)(((in->m + k.ranges - 1) / k.ranges + 63) / 64 * 64);
-	if (k.range_len == 0)
-		k.range_len = 64;
-
-	{ /* what no walk may reach: entries that are NA, NOCONN or DROP, queue entries of no taken connection */
-		const struct gcl_tcprxo_out *oo = ooo->out;
-		const size_t nq = ooo->in->nq;
-
-		if ((in->m && (hipMemsetAsync(oo->oflags, 0, in->m, s) != hipSuccess ||
-		               hipMemsetAsync(oo->skip, 0, 2 * (size_t)in->m, s) != hipSuccess)) ||
-		    (nq && (hipMemsetAsync(oo->qin_state, GCL_OOOQ_UNTOUCHED, nq, s) != hipSuccess ||
-		            hipMemsetAsync(oo->qin_skip, 0, 2 * nq, s) != hipSuccess ||
-		            hipMemsetAsync(oo->qin_len, 0, 2 * nq, s) != hipSuccess ||
-		            hipMemsetAsync(oo->qin_dst_off, 0, 8 * nq, s) != hipSuccess)))
-			return -EIO;
-		if (in->nconn == 0 && (hipMemsetAsync(oo->qout_off, 0, 4, s) != hipSuccess ||
-		                       hipMemsetAsync(oo->totals, 0, 8, s) != hipSuccess))
-			return -EIO;
-	}
-	if (in->m) { /* NA, NOCONN and DROP entries, and with nconn == 0 every entry */
-		const struct gcl_tcprxs_out *so = sts->out;
-
-		if (hipMemsetAsync(so->ev, 0, in->m, s) != hipSuccess ||
-		    hipMemsetAsync(so->rst_seq, 0, 4 * (size_t)in->m, s) != hipSuccess ||
-		    hipMemsetAsync(so->state_after, 0, in->m, s) != hipSuccess)
-			return -EIO;
-	}
-	if (in->nconn == 0) { /* every TCP segment is NOCONN: nothing to group, walk or lay out */
-		if (in->m)
-			hipLaunchKernelGGL(rx_parse_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
-		if (hipMemsetAsync(out->conn_off, 0, sizeof(uint64_t), s) != hipSuccess)
-			return -EIO;
-		return hipGetLastError() == hipSuccess ? 0 : -EIO;
-	}
-	if (hipMemsetAsync(k.run, 0, 8 * (size_t)in->nconn, s) != hipSuccess)
-		return -EIO;
-	const uint32_t *sorted = k.idx[g.passes - 1];
-	if (in->m) {
-		hipLaunchKernelGGL(rx_parse_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
-		for (uint32_t p = 0; p < g.passes; p++) {
-			const RxPass ps = {p ? k.idx[0] : nullptr, k.idx[p], p * kRxDigitBits, g.nb[p], g.kbits[p]};
-			const RxHistIo io = {k.hist, k.tot};
-			const uint32_t total = ps.nb * k.ranges;
-			const uint32_t nchunks = (total + kRxChunk - 1) / kRxChunk;
-			const dim3 grid((k.ranges + kRxWaves - 1) / kRxWaves);
-			hipLaunchKernelGGL(rx_count_kernel, grid, dim3(kRxThreads), 0, s, k, ps);
-			hipLaunchKernelGGL(rx_scan_sum_kernel<RxHistIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, total, k.csum);
-			hipLaunchKernelGGL(rx_scan_top_kernel<RxHistIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, k.csum, nchunks);
-			hipLaunchKernelGGL(rx_scan_apply_kernel<RxHistIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, total,
-			                   k.csum);
-			hipLaunchKernelGGL(rx_scatter_kernel, grid, dim3(kRxThreads), 0, s, k, ps);
+		if (sts) {
+			const RxsParams ks = {ko, sts->state, sts->out->ev, sts->out->rst_seq, sts->out->state_after,
+			                      sts->out->state_out};
+			hipLaunchKernelGGL(rxq_walk_kernel<RxsParams>, wgrid, dim3(kRxThreads), 0, s, ks, sorted);
+		} else {
+			hipLaunchKernelGGL(rxq_walk_kernel<RxoParams>, wgrid, dim3(kRxThreads), 0, s, ko, sorted);
 		}
-		hipLaunchKernelGGL(rx_runs_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k, sorted);
+		rx_scan(RxQoutIo{ko.qmeta, ko.qout_off, ko.totals, in->nconn}, in->nconn, ko.qsum, s);
+	} else if (full) {
+		hipLaunchKernelGGL(rxf_walk_kernel, wgrid, dim3(kRxThreads), 0, s, kf, sorted);
+	} else {
+		hipLaunchKernelGGL(rx_walk_kernel, wgrid, dim3(kRxThreads), 0, s, k, sorted);
 	}
-	RxfParams kf = {k, nullptr, nullptr, nullptr};
-	RxoParams ko = {};
-	const dim3 wgrid((in->nconn + kRxWaves - 1) / kRxWaves);
-	{
-		kf.rep_acks = full->rep_acks;
-		kf.out_ext = (uint4 *)full->out_ext;
-		kf.xcnt = (uint4 *)(ws + g.bytes);
-	}
-	{
-		const struct gcl_tcprxo_in *oi = ooo->in;
-		const struct gcl_tcprxo_out *oo = ooo->out;
-		uint8_t *at = ws + g.bytes + 16 * (size_t)in->nconn;
-
-		ko.f = kf;
-		ko.q_off = oi->q_off;
-		ko.q = (const uint4 *)oi->q;
-		ko.nq = oi->nq;
-		ko.q_out_cap = oi->q_out_cap;
-		ko.oflags = oo->oflags;
-		ko.skip = oo->skip;
-		ko.qin_state = oo->qin_state;
-		ko.qin_skip = oo->qin_skip;
-		ko.qin_len = oo->qin_len;
-		ko.qin_dst_off = (unsigned long long *)oo->qin_dst_off;
-		ko.qout_off = oo->qout_off;
-		ko.qout = (uint4 *)oo->qout;
-		ko.totals = (unsigned long long *)oo->totals;
-		ko.ocnt = (uint4 *)at;
-		at += 16 * (size_t)in->nconn;
-		ko.qmeta = (uint4 *)at;
-		at += 16 * (size_t)in->nconn;
-		ko.qsum = (uint32_t *)at;
-		at += rx_up16(4 * (((size_t)in->nconn + kRxChunk - 1) / kRxChunk));
-		ko.stage = (uint4 *)at;
-		const RxsParams ks = {ko, sts->state, sts->out->ev, sts->out->rst_seq, sts->out->state_after,
-		                      sts->out->state_out};
-		hipLaunchKernelGGL(rxs_walk_kernel, wgrid, dim3(kRxThreads), 0, s, ks, sorted);
-		const RxQoutIo io = {ko.qmeta, ko.qout_off, ko.totals, in->nconn};
-		const uint32_t nchunks = (in->nconn + kRxChunk - 1) / kRxChunk;
-		hipLaunchKernelGGL(rx_scan_sum_kernel<RxQoutIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn, ko.qsum);
-		hipLaunchKernelGGL(rx_scan_top_kernel<RxQoutIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, ko.qsum, nchunks);
-		hipLaunchKernelGGL(rx_scan_apply_kernel<RxQoutIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn,
-		                   ko.qsum);
-	}
-	{
-		const RxConnIo io = {k.conn, k.out_conn, k.conn_off, in->nconn, k.amask};
-		const uint32_t nchunks = (in->nconn + kRxChunk - 1) / kRxChunk;
-		hipLaunchKernelGGL(rx_scan_sum_kernel<RxConnIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn, k.lsum);
-		hipLaunchKernelGGL(rx_scan_top_kernel<RxConnIo>, dim3(1), dim3(kRxTopThreads), 0, s, io, k.lsum, nchunks);
-		hipLaunchKernelGGL(rx_scan_apply_kernel<RxConnIo>, dim3(nchunks), dim3(kRxThreads), 0, s, io, in->nconn,
-		                   k.lsum);
-	}
-	const dim3 cgrid(std::min<uint32_t>((in->nconn + kRxThreads - 1) / kRxThreads, cus * 2));
-	{
-		if (in->m)
-			hipLaunchKernelGGL(rxf_fix_kernel, dim3(egrid), dim3(kRxThreads), 0, s, k);
+	rx_scan(RxConnIo{k.conn, k.out_conn, k.conn_off, in->nconn, k.amask}, in->nconn, k.lsum, s);
+	if (in->m && full)
+		hipLaunchKernelGGL(rx_fix_kernel<true>, dim3(egrid), dim3(kRxThreads), 0, s, k);
+	else if (in->m)
+		hipLaunchKernelGGL(rx_fix_kernel<false>, dim3(egrid), dim3(kRxThreads), 0, s, k);
+	if (ooo)
 		hipLaunchKernelGGL(rxo_qout_kernel, wgrid, dim3(kRxThreads), 0, s, ko);
-		if (counts)
-			hipLaunchKernelGGL(rxo_counts_kernel, cgrid, dim3(kRxThreads), 0, s, ko);
+	if (counts) {
+		const dim3 cgrid(std::min<uint32_t>((in->nconn + kRxThreads - 1) / kRxThreads, cus * 2));
+		if (ooo)
+			hipLaunchKernelGGL(rx_counts_kernel<16>, cgrid, dim3(kRxThreads), 0, s, ko);
+		else if (full)
+			hipLaunchKernelGGL(rx_counts_kernel<10>, cgrid, dim3(kRxThreads), 0, s, kf);
+		else
+			hipLaunchKernelGGL(rx_counts_kernel<5>, cgrid, dim3(kRxThreads), 0, s, k);
 	}
 	return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
@@ -1989,7 +1634,7 @@ extern "C" int gcl_tcp_rx(struct gcl_ctx *c, const struct gcl_batch *b, const st
                           const struct gcl_tcprx_out *out, uint64_t *counts, void *workspace,
                           size_t workspace_bytes, void *hip_stream)
 {
-	return rx_run(c, b, in, out, nullptr, nullptr, counts, workspace, workspace_bytes, hip_stream);
+	return rx_run(c, b, in, out, nullptr, nullptr, nullptr, counts, workspace, workspace_bytes, hip_stream);
 }
 
 extern "C" int gcl_tcp_rx_full_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, size_t *bytes)
@@ -2012,7 +1657,7 @@ extern "C" int gcl_tcp_rx_full(struct gcl_ctx *c, const struct gcl_batch *b, con
 	                                 in->conn, in->nconn, in->blocks};
 	const RxFull full = {in->rep_acks, out_ext};
 
-	return rx_run(c, b, &rin, out, &full, nullptr, counts, workspace, workspace_bytes, hip_stream);
+	return rx_run(c, b, &rin, out, &full, nullptr, nullptr, counts, workspace, workspace_bytes, hip_stream);
 }
 
 extern "C" int gcl_tcp_rx_ooo_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, uint32_t nq, size_t *bytes)
@@ -2037,7 +1682,7 @@ extern "C" int gcl_tcp_rx_ooo(struct gcl_ctx *c, const struct gcl_batch *b, cons
 	const RxFull full = {in->rep_acks, out_ext};
 	const RxOoo o = {in, ooo};
 
-	return rx_run(c, b, &rin, out, &full, &o, counts, workspace, workspace_bytes, hip_stream);
+	return rx_run(c, b, &rin, out, &full, &o, nullptr, counts, workspace, workspace_bytes, hip_stream);
 }
 
 extern "C" int gcl_tcp_rx_states_workspace(uint64_t m, uint32_t nconn, uint32_t blocks, uint32_t nq, size_t *bytes)
@@ -2061,5 +1706,5 @@ extern "C" int gcl_tcp_rx_states(struct gcl_ctx *c, const struct gcl_batch *b, c
 	const RxOoo o = {&oin, ooo};
 	const RxStates ss = {in->state, st};
 
-	return rxs_run(c, b, &rin, out, &full, &o, &ss, counts, workspace, workspace_bytes, hip_stream);
+	return rx_run(c, b, &rin, out, &full, &o, &ss, counts, workspace, workspace_bytes, hip_stream);
 }

@@ -721,11 +721,13 @@ S_OUT = (("ev", np.uint8, "m"), ("rst_seq", np.uint32, "m"), ("state_after", np.
          ("state_out", np.uint8, "nconn"))
 
 
-def blank(case):
+def blank(case, fill=SENTINEL):
     z = oc.sizes(case)
     b = oc.blank(case)
     for f, dt, by in S_OUT:
         b[f] = np.frombuffer(bytes([SENTINEL]) * (np.dtype(dt).itemsize * (z[by] + GUARD)), dtype=dt).copy()
+    if fill != SENTINEL:
+        b = {f: np.full(a.nbytes, fill, dtype=np.uint8).view(a.dtype) for f, a in b.items()}
     return b
 
 
@@ -740,10 +742,10 @@ def compare(got, want, case, what):
         assert not len(bad), f"{what}: {f}[{bad[0]}] = {g[bad[0]]} != {want[f][bad[0]]} ({len(bad)} differ)"
 
 
-def run_host(g, case, counts=True):
+def run_host(g, case, counts=True, fill=SENTINEL):
     """gcl_tcp_rx_states_host over sentinel-filled outputs: (outputs, counts)"""
     z = oc.sizes(case)
-    out = blank(case)
+    out = blank(case, fill)
     cnt = np.full(NR, 5, dtype=np.uint64) if counts else None
     g.tcp_rx_states_host(case["frames"], case["pkt_len"], case["sock"], case["conn"], stride=case["stride"],
                          offs=case["offs"], frames_len=case["frames_len"], order=case.get("order"), m=z["m"],

@@ -48,12 +48,12 @@ def dev(a):
     return torch.from_numpy(a.view(SIGNED.get(a.dtype, a.dtype))).cuda()
 
 
-def run_gpu(g, clf, case, counts=True, calls=1, keep=None, blocks=None):
-    """@calls calls over sentinel-filled device outputs: (outputs as numpy, counts summed over the calls)"""
+def run_gpu(g, clf, case, counts=True, calls=1, keep=None, blocks=None, workspace=None, fill=sc.SENTINEL):
+    """@calls calls over @fill-filled device outputs: (outputs as numpy, counts summed over the calls)"""
     z = oc.sizes(case)
     m, nconn, nq = z["m"], z["nconn"], z["nq"]
     n, order = len(case["pkt_len"]), case.get("order")
-    blank = sc.blank(case)
+    blank = sc.blank(case, fill)
     out = {f: dev(a) for f, a in blank.items()}
     frames, plen = dev(case["frames"]), dev(case["pkt_len"]) if n else torch.zeros(1, dtype=torch.int16, device="cuda")
     offs = dev(case["offs"]) if case["offs"] is not None and n else None
@@ -70,7 +70,7 @@ def run_gpu(g, clf, case, counts=True, calls=1, keep=None, blocks=None):
                           order=dev(order) if order is not None else None, m=m, l4_status=st,
                           align=case.get("align", 0), blocks=case.get("blocks", 0) if blocks is None else blocks,
                           rep_acks=rep, q_off=q_off, q=q, nq=nq, q_out_cap=z["cap"], state=state, out=out,
-                          counts=cnt)
+                          counts=cnt, workspace=workspace)
     torch.cuda.synchronize()
     if keep is not None:
         keep.update(out, frames=frames, sock=sock)
@@ -87,7 +87,7 @@ def check(g, clf, case, what, **kw):
     return got
 
 
-@pytest.mark.parametrize("blocks", [0, 1, 3])
+@pytest.mark.parametrize("blocks", [0, 1, 3, rc.MAX_BLOCKS])
 def test_named_cases_against_host_twin_and_reference(g, clf, blocks):
     total = 0
     for name in sr.names():
@@ -162,6 +162,45 @@ def test_input_queue_of_64_with_a_fin_entry(g, clf, pos):
 @pytest.mark.parametrize("nconn", [1, WAVES - 1, WAVES + 1, 1000])
 def test_connection_counts(g, clf, nconn):
     check(g, clf, sc.random_case(100 + nconn, nconn=nconn, data=(1, 4)), nconn)
+
+
+@pytest.mark.parametrize("nconn", [rc.PASS_CONN, rc.PASS_CONN + 1])
+def test_one_and_two_grouping_passes(g, clf, nconn):
+    """connections 0, PASS_CONN - 1 and nconn - 1 (cookies at both ends of the
+    range, the last one in the second pass's second digit) get 65 in-order
+    10-byte segments each, interleaved; the last connection enters in
+    SYN_RECEIVED and its 65th segment, the first of its second chunk, carries
+    the peer's FIN"""
+    rng = np.random.default_rng(nconn)
+    live, last = sorted({0, rc.PASS_CONN - 1, nconn - 1}), nconn - 1
+    segs = [rc.seg(rng, c, 100 + 10 * k, 10, flags=TCP_ACK | (TCP_FIN if (c, k) == (last, 64) else 0))
+            for k in range(65) for c in live]
+    case = rc.build([rc.conn1(snd_wl1=50000)] * nconn, segs)
+    case["state"] = np.full(nconn, sc.ESTABLISHED, dtype=np.uint8)
+    case["state"][last] = sc.SYN_RECEIVED
+    got = check(g, clf, case, nconn)
+    assert got["out_conn"]["nfast"][live].tolist() == [65] * len(live)
+    assert got["state_out"][live].tolist() == [sc.ESTABLISHED] * (len(live) - 1) + [sc.CLOSE_WAIT]
+    assert int(got["out_conn"]["rcv_nxt"][last]) == 100 + 650 + 1
+    assert int(got["ev"][live.index(last)]) & sc.EV_STATE and int(got["ev"][len(segs) - 1]) == sc.EV_STATE | sc.EV_FIN
+
+
+def test_dirty_workspace_reused_and_counts_accumulate(g, clf):
+    """the workspace and every output filled with 0xFF, then two calls on the
+    same buffers: every byte of every output is what the host twin leaves in
+    buffers filled the same way, and counts holds twice the twin's counters,
+    the four the walk adds itself among them"""
+    case = sc.stream("lifetimes")
+    z = oc.sizes(case)
+    need = g.tcp_rx_states_workspace(z["m"], z["nconn"], 0, z["nq"])
+    ws = torch.full((need,), 0xFF, dtype=torch.uint8, device="cuda")
+    want, hcnt = sc.run_host(g, case, fill=0xFF)
+    got, cnt = run_gpu(g, clf, case, calls=2, workspace=ws, fill=0xFF)
+    for f in want:
+        bad = np.nonzero(got[f].view(np.uint8) != want[f].view(np.uint8))[0]
+        assert not len(bad), f"{f}: byte {bad[0]} of {len(bad)} that differ"
+    assert cnt.tolist() == (hcnt * np.uint64(2)).tolist()
+    assert all(int(hcnt[k]) > 3 for k in (sc.C_RSTS, sc.C_FAILS, sc.C_FINS, sc.C_STATE_CHANGES))
 
 
 def test_empty_list(g, clf):
