@@ -19,6 +19,7 @@
 #include "gcl_tcptmr.h"
 #include "gcl_txq.h"
 #include "gcl_txh.h"
+#include "gcl_udprx.h"
 
 #define ROT(x, k) (((x) << (k)) | ((x) >> (32 - (k))))
 
@@ -1766,6 +1767,116 @@ int gcl_tcp_rx_open_host(const struct gcl_batch *b, const struct gcl_tcpopen_in 
 	c[GCL_OPENC_SEGSKIP] = at - seg->totals[1];
 	if (counts)
 		for (int k = 0; k < GCL_OPENC_NR; k++)
+			counts[k] += c[k];
+	return 0;
+}
+
+/* One list entry of gcl_udp_rx: the frame's bytes [12, 48) as dwords, gcl_pay_rule's
+ * word on them and gcl_udprx_class.  Returns the verdict so far (NA, NOSOCK, or
+ * QUEUED for a datagram of socket *s). */
+static uint32_t udprx_entry(const struct gcl_batch *b, const struct gcl_udprx_in *in, uint64_t j,
+                            struct gcl_pay_desc *r, uint32_t *s)
+{
+	const uint64_t i = in->order ? in->order[j] : j;
+
+	*s = GCL_UDPRX_NONE;
+	if (i >= b->n)
+		return GCL_UDPRX_NA;
+	const uint64_t raw = b->offs ? b->offs[i] : i * b->stride;
+	const uint64_t o = raw < b->frames_len ? raw : b->frames_len;
+	const uint64_t avail = b->frames_len - o;
+	const uint64_t L = b->pkt_len[i] < avail ? b->pkt_len[i] : avail;
+	uint8_t h[48] = {0};
+	uint32_t d[9];
+
+	if (avail)
+		memcpy(h, b->frames + o, avail < sizeof(h) ? avail : sizeof(h));
+	for (int x = 0; x < 9; x++)
+		d[x] = h[12 + 4 * x] | (uint32_t)h[13 + 4 * x] << 8 | (uint32_t)h[14 + 4 * x] << 16 |
+		       (uint32_t)h[15 + 4 * x] << 24;
+	*r = gcl_pay_rule(d, o, L, in->l4_status != NULL, in->l4_status ? in->l4_status[i] : 0, 1, in->sock[i]);
+	return gcl_udprx_class(r, in->sock[i], in->sock_base, in->nsock, s);
+}
+
+/* The rule of gcl_udp_rx (gclassify.h) on the CPU, taken literally: one walk
+ * over the list in order with every socket's running inq_len kept in out_sock,
+ * gcl_udprx_step of gcl_udprx.h for every datagram as udp_conn_recv does it
+ * under the lock (not the closed form the kernels use); then the layout, and a
+ * second walk for dst_off, rec_idx and the records. */
+int gcl_udp_rx_host(const struct gcl_batch *b, const struct gcl_udprx_in *in,
+                    const struct gcl_udprx_out *out, uint64_t *counts)
+{
+	uint64_t c[GCL_UDPRXC_NR] = {0}, at = 0;
+	uint32_t nrec = 0;
+
+	if (gcl_udprx_refused(b, in, out, counts))
+		return -EINVAL;
+	const uint32_t amask = in->align ? in->align - 1 : 0;
+
+	for (uint32_t s = 0; s < in->nsock; s++) {
+		memset(&out->out_sock[s], 0, sizeof(out->out_sock[s]));
+		out->out_sock[s].inq_len = in->usock[s].inq_len;
+		out->sock_off[s] = 0;
+	}
+	for (uint64_t j = 0; j < in->m; j++) {
+		struct gcl_pay_desc r;
+		uint32_t s, sf = 0, len = 0, idx = GCL_UDPRX_NONE;
+		uint32_t verdict = udprx_entry(b, in, j, &r, &s);
+		uint64_t off = 0;
+
+		if (verdict == GCL_UDPRX_QUEUED) {
+			struct gcl_udp_sock_out *o = &out->out_sock[s];
+			int32_t run = o->inq_len;
+
+			verdict = gcl_udprx_step(&run, in->usock[s].inq_cap, in->usock[s].flags, &sf);
+			o->inq_len = run;
+			o->flags |= (uint8_t)sf;
+			if (gcl_udprx_taken(verdict)) {
+				len = r.len;
+				/* for now the record and the offset inside the socket's region */
+				idx = o->ntaken++;
+				off = out->sock_off[s];
+				out->sock_off[s] += gcl_pay_pad(len, amask);
+				c[GCL_UDPRXC_BYTES] += len;
+				c[GCL_UDPRXC_POLLINS] += (sf & GCL_UDPRX_SF_POLLIN) != 0;
+			} else {
+				o->ndropped++;
+			}
+		}
+		out->verdict[j] = (uint8_t)verdict;
+		out->sflags[j] = (uint8_t)sf;
+		out->copy_len[j] = (uint16_t)len;
+		out->dst_off[j] = off;
+		out->rec_idx[j] = idx;
+		c[verdict]++;
+	}
+	for (uint32_t s = 0; s < in->nsock; s++) {
+		const uint64_t bytes = out->sock_off[s];
+
+		out->rec_off[s] = nrec;
+		out->sock_off[s] = at;
+		nrec += out->out_sock[s].ntaken;
+		at += bytes;
+	}
+	out->rec_off[in->nsock] = nrec;
+	out->sock_off[in->nsock] = at;
+	for (uint64_t j = 0; j < in->m; j++)
+		if (gcl_udprx_taken(out->verdict[j])) {
+			struct gcl_pay_desc r;
+			struct gcl_udp_rec *rec;
+			uint32_t s;
+
+			(void)udprx_entry(b, in, j, &r, &s);
+			out->dst_off[j] += out->sock_off[s];
+			out->rec_idx[j] += out->rec_off[s];
+			rec = &out->rec[out->rec_idx[j]];
+			rec->dst_off = out->dst_off[j];
+			rec->rip = r.meta[0];
+			rec->rport = (uint16_t)gcl_udprx_rport(&r);
+			rec->len = (uint16_t)r.len;
+		}
+	if (counts)
+		for (int k = 0; k < GCL_UDPRXC_NR; k++)
 			counts[k] += c[k];
 	return 0;
 }

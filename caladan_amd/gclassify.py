@@ -183,6 +183,19 @@ TCP_OPEN_DTYPE = np.dtype([("src", "<u4"), ("listener", "<u4"), ("lip", "<u4"), 
 # gcl_tcp_txq: the want bits, the entry flag, the state byte, the connection flags, the counters,
 # the caps, struct gcl_txq_ent, struct gcl_txq_cold and struct gcl_txq_conn_out
 TXQ_W_RTO, TXQ_W_FAST, TXQ_W_EXCL = 0x01, 0x02, 0x04
+# gcl_udp_rx: the verdict byte (also the first counter slots), the counters, sflags, the socket flags,
+# the caps, struct gcl_udp_sock, struct gcl_udp_sock_out and struct gcl_udp_rec
+UDPRX_QUEUED, UDPRX_SPAWN, UDPRX_FULL, UDPRX_CLOSED, UDPRX_NOSOCK, UDPRX_NA = range(6)
+UDPRX_NR_VERDICTS, UDPRXC_BYTES, UDPRXC_POLLINS, UDPRXC_NR = 6, 6, 7, 8
+UDPRX_SF_POLLIN = 0x01
+UDPS_SHUTDOWN, UDPS_ERR, UDPS_SPAWNER = 0x01, 0x02, 0x04
+UDPRX_MAX_BLOCKS, UDPRX_MAX_SOCK, UDPRX_NONE = 1024, 1 << 20, 0xFFFFFFFF
+# its grouping (csrc/gcl_udprx.hip): the sockets one counting-sort pass serves
+UDPRX_PASS_SOCK = 2048
+UDP_SOCK_DTYPE = np.dtype([("inq_len", "<i4"), ("inq_cap", "<i4"), ("flags", "u1"), ("pad", "u1", (7,))])
+UDP_SOCK_OUT_DTYPE = np.dtype([("inq_len", "<i4"), ("ntaken", "<u4"), ("ndropped", "<u4"), ("flags", "u1"),
+                               ("pad", "u1", (3,))])
+UDP_REC_DTYPE = np.dtype([("dst_off", "<u8"), ("rip", "<u4"), ("rport", "<u2"), ("len", "<u2")])
 TXQE_INFLIGHT = 0x01
 TXQS_KEPT, TXQS_ACKED, TXQS_RETX, TXQS_RETX_COPY, TXQS_NOSPACE, TXQS_REFUSED = range(6)
 TXQS_TRIMMED = 0x80
@@ -529,6 +542,21 @@ class GclTcpopenOut(ctypes.Structure):
     _fields_ = [(f, ctypes.c_void_p) for f in TCPOPEN_OUT_FIELDS]
 
 
+class GclUdprxIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("align", ctypes.c_uint32), ("order", ctypes.c_void_p),
+                ("m", ctypes.c_uint64), ("sock", ctypes.c_void_p), ("l4_status", ctypes.c_void_p),
+                ("usock", ctypes.c_void_p), ("nsock", ctypes.c_uint32), ("sock_base", ctypes.c_uint32),
+                ("blocks", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+UDPRX_ENTRY_FIELDS = ("verdict", "sflags", "copy_len", "dst_off", "rec_idx")
+UDPRX_OUT_FIELDS = UDPRX_ENTRY_FIELDS + ("rec", "out_sock", "rec_off", "sock_off")
+
+
+class GclUdprxOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in UDPRX_OUT_FIELDS]
+
+
 class GclTxqIn(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("now", ctypes.c_uint64),
                 ("qoff", ctypes.c_void_p), ("ent", ctypes.c_void_p), ("cold", ctypes.c_void_p),
@@ -546,6 +574,8 @@ class GclTxqOut(ctypes.Structure):
 
 
 assert ctypes.sizeof(GclTxqIn) == 96 and ctypes.sizeof(GclTxqOut) == 80
+assert ctypes.sizeof(GclUdprxIn) == 64 and ctypes.sizeof(GclUdprxOut) == 72
+assert UDP_SOCK_DTYPE.itemsize == 16 and UDP_SOCK_OUT_DTYPE.itemsize == 16 and UDP_REC_DTYPE.itemsize == 16
 assert TXQ_ENT_DTYPE.itemsize == 16 and TXQ_COLD_DTYPE.itemsize == 16 and TXQ_CONN_OUT_DTYPE.itemsize == 32
 assert ctypes.sizeof(GclTickIn) == 64 and ctypes.sizeof(GclTickOut) == 56 and ctypes.sizeof(GclRxackIn) == 104
 assert ctypes.sizeof(GclCtlsegOut) == 48 and TCP_TMR_DTYPE.itemsize == 64 and TCP_TMR_OUT_DTYPE.itemsize == 32
@@ -699,6 +729,11 @@ def _load():
                                   ctypes.c_size_t, vp]),
         "gcl_tcp_rx_open_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclTcpopenIn),
                                        ctypes.POINTER(GclTcpopenOut), ctypes.POINTER(GclCtlsegOut), vp]),
+        "gcl_udp_rx_workspace": (i32, [u64, u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_udp_rx": (i32, [vp, ctypes.POINTER(GclBatch), ctypes.POINTER(GclUdprxIn),
+                             ctypes.POINTER(GclUdprxOut), vp, vp, ctypes.c_size_t, vp]),
+        "gcl_udp_rx_host": (i32, [ctypes.POINTER(GclBatch), ctypes.POINTER(GclUdprxIn),
+                                  ctypes.POINTER(GclUdprxOut), vp]),
         "gcl_tcp_txq_workspace": (i32, [u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
         "gcl_tcp_txq": (i32, [vp, ctypes.POINTER(GclTxqIn), ctypes.POINTER(GclTxqOut), vp, vp,
                               ctypes.c_size_t, vp]),
@@ -1633,6 +1668,69 @@ def tcp_rx_open_workspace(m, nlisten, blocks=0, hash_slots=0):
     return need.value
 
 
+def _udprx_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status, usock, nsock,
+                   sock_base, align, blocks, out, counts):
+    """The three structs of gcl_udp_rx / gcl_udp_rx_host, sizes checked; @out
+    maps UDPRX_OUT_FIELDS to buffers."""
+    if sock is None:
+        raise ValueError("sock is required")
+    for arr, w in ((offs, 8), (pkt_len, 2), (sock, 4), (l4_status, 1)):
+        if arr is not None and _nbytes(arr) < w * n:
+            raise ValueError("per-packet array too small")
+    for arr, w in ((order, 4), (out["verdict"], 1), (out["sflags"], 1), (out["copy_len"], 2),
+                   (out["dst_off"], 8), (out["rec_idx"], 4), (out["rec"], 16)):
+        if arr is not None and _nbytes(arr) < w * m:
+            raise ValueError("per-entry array too small")
+    for arr, w in ((usock, 16), (out["out_sock"], 16)):
+        if arr is not None and _nbytes(arr) < w * nsock:
+            raise ValueError("per-socket array too small")
+    for f, w in (("rec_off", 4), ("sock_off", 8)):
+        if out[f] is not None and _nbytes(out[f]) < w * (nsock + 1):
+            raise ValueError(f + " too small")
+    if counts is not None and _nbytes(counts) < 8 * UDPRXC_NR:
+        raise ValueError("counts buffer too small")
+    b = GclBatch(frames=_ptr(frames), frames_len=_frames_len(frames, frames_len), stride=stride,
+                 offs=_ptr(offs), olflags=None, rss=None, fdir_hi=None, pkt_len=_ptr(pkt_len), n=n,
+                 dst_hint=None)
+    rin = GclUdprxIn(size=ctypes.sizeof(GclUdprxIn), align=align, order=_ptr(order), m=m, sock=_ptr(sock),
+                     l4_status=_ptr(l4_status), usock=_ptr(usock), nsock=nsock, sock_base=sock_base,
+                     blocks=blocks, pad=0)
+    rout = GclUdprxOut(**{f: _ptr(out[f]) for f in UDPRX_OUT_FIELDS})
+    return b, rin, rout
+
+
+def udp_rx_host(frames, pkt_len, sock, usock, stride=0, offs=None, n=None, frames_len=None, order=None,
+                m=None, l4_status=None, nsock=None, sock_base=0, align=0, blocks=0, out=None, counts=None):
+    """gcl_udp_rx_host: the rule of Classifier.udp_rx on the CPU over numpy
+    arrays.  @usock is a UDP_SOCK_DTYPE array; cookie c names
+    usock[c - sock_base].  @out maps UDPRX_OUT_FIELDS to arrays (u8, u8, u16,
+    u64, u32, UDP_REC_DTYPE[m], UDP_SOCK_OUT_DTYPE[nsock], u32[nsock + 1],
+    u64[nsock + 1]); the ones left out are allocated.  @counts is a
+    u64[UDPRXC_NR], accumulated.  Returns the dict."""
+    n = len(pkt_len) if n is None else n
+    m = _pay_m(n, m, order)
+    nsock = len(usock) if nsock is None else nsock
+    out = dict(out or {})
+    for f, dt, k in (("verdict", np.uint8, m), ("sflags", np.uint8, m), ("copy_len", np.uint16, m),
+                     ("dst_off", np.uint64, m), ("rec_idx", np.uint32, m), ("rec", UDP_REC_DTYPE, m),
+                     ("out_sock", UDP_SOCK_OUT_DTYPE, nsock), ("rec_off", np.uint32, nsock + 1),
+                     ("sock_off", np.uint64, nsock + 1)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    b, rin, rout = _udprx_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock, l4_status,
+                                  usock, nsock, sock_base, align, blocks, out, counts)
+    _check(lib.gcl_udp_rx_host(ctypes.byref(b), ctypes.byref(rin), ctypes.byref(rout), _ptr(counts)),
+           "gcl_udp_rx_host")
+    return out
+
+
+def udp_rx_workspace(m, nsock, blocks=0):
+    """gcl_udp_rx_workspace: bytes of device scratch a call over @m entries and @nsock sockets takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_udp_rx_workspace(m, nsock, blocks, ctypes.byref(need)), "gcl_udp_rx_workspace")
+    return need.value
+
+
 def tcp_tick_workspace(nconn, blocks=0):
     """gcl_tcp_tick_workspace: bytes of device scratch a sweep of @nconn connections takes."""
     need = ctypes.c_size_t()
@@ -2539,6 +2637,45 @@ class Classifier:
         _check(lib.gcl_tcp_rx_open(self._ctx, ctypes.byref(b), ctypes.byref(oin), ctypes.byref(oout),
                                    ctypes.byref(seg), _ptr(counts), _ptr(workspace), _nbytes(workspace), stream),
                "gcl_tcp_rx_open")
+        return out
+
+    def udp_rx(self, frames, n, pkt_len, sock, usock, nsock, stride=0, offs=None, frames_len=None,
+               order=None, m=None, l4_status=None, sock_base=0, align=0, blocks=0, out=None, counts=None,
+               workspace=None, stream=None):
+        """gcl_udp_rx: udp_conn_recv and udp_par_recv for one runtime's list
+        @order[0..m) (None: every packet in turn) on the GPU, asynchronous.
+        @sock is what sock_lookup wrote, @l4_status what l4_csum(L4_VERIFY)
+        wrote, @usock a device uint8[nsock, 16] holding UDP_SOCK_DTYPE records
+        (16-B aligned); cookie c names usock[c - sock_base].  @out maps
+        UDPRX_OUT_FIELDS to device buffers; the ones left out are allocated on
+        @frames' device (verdict and sflags uint8, copy_len int16, dst_off and
+        sock_off int64, rec_idx and rec_off int32, rec uint8[m, 16], out_sock
+        uint8[nsock, 16]).  @counts is a device u64[UDPRXC_NR], accumulated.
+        The scratch is @workspace, or a torch tensor kept on the classifier.
+        Returns the dict: with l4_payload's src_off, copy_len and dst_off are
+        copy_batch's length and dst_off."""
+        import torch
+        m = _pay_m(n, m, order)
+        dev = frames.device if hasattr(frames, "device") else None
+        out = dict(out or {})
+        mm = max(m, 1)
+        for f, dt, shape in (("verdict", torch.uint8, (mm,)), ("sflags", torch.uint8, (mm,)),
+                             ("copy_len", torch.int16, (mm,)), ("dst_off", torch.int64, (mm,)),
+                             ("rec_idx", torch.int32, (mm,)), ("rec", torch.uint8, (mm, 16)),
+                             ("out_sock", torch.uint8, (max(nsock, 1), 16)),
+                             ("rec_off", torch.int32, (nsock + 1,)), ("sock_off", torch.int64, (nsock + 1,))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        b, rin, rout = _udprx_structs(frames, n, stride, offs, pkt_len, frames_len, m, order, sock,
+                                      l4_status, usock, nsock, sock_base, align, blocks, out, counts)
+        ws = workspace
+        if ws is None:
+            need = udp_rx_workspace(m, nsock, blocks)
+            ws = getattr(self, "_udprx_ws", None)
+            if ws is None or ws.numel() < need or ws.device != out["sock_off"].device:
+                ws = self._udprx_ws = torch.empty(need, dtype=torch.uint8, device=out["sock_off"].device)
+        _check(lib.gcl_udp_rx(self._ctx, ctypes.byref(b), ctypes.byref(rin), ctypes.byref(rout),
+                              _ptr(counts), _ptr(ws), _nbytes(ws), stream), "gcl_udp_rx")
         return out
 
     def tcp_txq(self, now, qoff, ent, cold, nent, conn, addr, nconn, seg_cap, want=None, frame_stride=64,

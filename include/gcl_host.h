@@ -330,6 +330,24 @@ int gcl_tcp_rx_open_host(const struct gcl_batch *b, const struct gcl_tcpopen_in 
                          const struct gcl_tcpopen_out *out, const struct gcl_ctlseg_out *seg, uint64_t *counts);
 
 /*
+ * gcl_udp_rx_host - the rule of gcl_udp_rx (gclassify.h) on the CPU over host
+ * pointers, taken literally: one walk over the list in order with every
+ * socket's running inq_len kept in out_sock, each datagram compared and pushed
+ * as udp_conn_recv does it under inq_lock (runtime/net/udp.c:89-100,
+ * gcl_udprx_step of csrc/gcl_udprx.h).  It does NOT use the closed form the
+ * kernels use (rank against inq_cap - inq_len), so the twin and the kernels
+ * check each other.  No grouping and no workspace; a second walk adds
+ * sock_off and rec_off and writes the records.  @b, @in and @out are
+ * gcl_udp_rx's structs with every pointer a host pointer (in->blocks is
+ * checked against GCL_UDPRX_MAX_BLOCKS and otherwise not looked at); @counts
+ * is a host u64[GCL_UDPRXC_NR], ACCUMULATED, may be NULL.  The same outputs
+ * byte for byte, the same counts and the same guarantee.  0, or -EINVAL for
+ * what gcl_udp_rx refuses (the ctx and the workspace apart).
+ */
+int gcl_udp_rx_host(const struct gcl_batch *b, const struct gcl_udprx_in *in,
+                    const struct gcl_udprx_out *out, uint64_t *counts);
+
+/*
  * gcl_tcp_txq_host - the rule of gcl_tcp_txq (gclassify.h) on the CPU over
  * host pointers, for the queues the GPU did not see: tcp_conn_ack
  * (runtime/net/tcp.c:217-238), tcp_tx_retransmit with tcp_tx_retransmit_one

@@ -2942,6 +2942,161 @@ int gcl_tcp_rx_open(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct
                     const struct gcl_tcpopen_out *out, const struct gcl_ctlseg_out *seg, uint64_t *counts,
                     void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/*
+ * UDP receive: the step behind gcl_l4_payload for UDP.  udp_conn_recv
+ * (runtime/net/udp.c:79-107) takes inq_lock, drops the datagram when the
+ * socket's ingress queue is full, in error or shut down, and otherwise pushes
+ * it, sets POLLIN when the queue was empty and signals a waiter;
+ * udp_par_recv (udp.c:811-840) hands a spawner's datagram to a new thread.
+ * gcl_udp_rx runs every UDP socket's datagrams of one runtime's list, in
+ * arrival order, through that step on the GPU, and lays the datagrams each
+ * socket took out contiguously and in arrival order:
+ *
+ *   gcl_classify -> gcl_sock_lookup -> gcl_l4_csum VERIFY -> gcl_plan ->
+ *   gcl_l4_payload -> gcl_udp_rx -> gcl_copy_batch (src_off from
+ *   gcl_l4_payload; len = copy_len and dst_off from this call).
+ *
+ * One call serves ONE runtime, as gcl_tcp_rx does: @in->order / m are that
+ * runtime's range of a plan.  A runtime's cookies are shared by its TCP
+ * connections, its listeners and its UDP sockets, so cookie c with
+ * sock_base <= c < sock_base + nsock names @in->usock[c - sock_base] (as
+ * gcl_tcp_rx_open has listen_base).  It works on every context and touches no
+ * table.
+ *
+ * List entry j names packet i = in->order ? in->order[j] : j.  It is a
+ * DATAGRAM exactly when gcl_l4_payload, given the same sock and l4_status,
+ * keeps it as GCL_PAY_UDP (the very function decides, gcl_pay_rule; it keeps no
+ * UDP packet with tot < 28, which is mbuf_pull_hdr_or_null failing, udp.c:84
+ * and :820); len is gcl_l4_payload's len.  The verdict of entry j is the first
+ * line that matches, the entries of a socket taken in list order:
+ *   not a datagram (OOR, NA, TCP, BADCSUM, NOSOCK)           GCL_UDPRX_NA
+ *   the cookie lies outside [sock_base, sock_base + nsock)   GCL_UDPRX_NOSOCK
+ *   GCL_UDPS_SPAWNER (udp_par_recv: no cap; ERR and
+ *     SHUTDOWN are not looked at)                            GCL_UDPRX_SPAWN
+ *   GCL_UDPS_ERR or GCL_UDPS_SHUTDOWN (udp.c:91, mbuf_drop)  GCL_UDPRX_CLOSED
+ *   the running inq_len >= inq_cap (udp.c:91)                GCL_UDPRX_FULL
+ *   otherwise: pushed, the running inq_len++                 GCL_UDPRX_QUEUED
+ * The running inq_len starts at usock[s].inq_len and only a QUEUED entry moves
+ * it; both words are the reference's ints and are compared as signed, so a
+ * socket that enters with inq_cap <= inq_len (negative values included) has
+ * every entry FULL, and nothing overflows.  The call works on a snapshot: no
+ * udp_read pops during it.  A datagram of len 0 is a datagram and takes a slot.
+ *
+ * Per-entry outputs (m elements each): verdict; sflags, GCL_UDPRX_SF_POLLIN on
+ * the QUEUED entry that found the running inq_len == 0 (udp.c:99-100);
+ * copy_len, len for QUEUED and SPAWN and 0 otherwise; dst_off (0 when nothing
+ * is copied); rec_idx, the entry's record or 0xFFFFFFFF.  Per socket,
+ * out_sock[s] holds inq_len after the list, ntaken (QUEUED or SPAWN: the
+ * runtime signals inq_wq that many times), ndropped (FULL + CLOSED) and
+ * GCL_UDPRX_SF_POLLIN in flags when some entry set it; a socket with no entry
+ * gets its inq_len back with zero counts.  rec_off[0, nsock] and
+ * sock_off[0, nsock] are the prefix sums over the sockets of ntaken and of the
+ * padded bytes taken, the last element the total.
+ *
+ * The layout, with pad() as in gcl_l4_payload and in->align: the k-th taken
+ * datagram of socket s, in arrival order, is rec[rec_off[s] + k] (dst_off,
+ * rip and rport in host order, len: what udp_read_from, udp.c:373-379, and
+ * udp_spawn_data, :833-838, need), and its bytes go to dst_off = sock_off[s] +
+ * the sum of pad(len) over the k taken before it.  gcl_copy_batch with
+ * copy_len and dst_off then leaves every socket's queue as one contiguous run
+ * of datagrams in arrival order; a dropped datagram is not copied.  Records at
+ * and past rec_off[nsock] are not written.
+ *
+ * Every pointer is a device pointer; each array is aligned to its element,
+ * usock, out_sock and rec to 16 B.  @counts is a device u64[GCL_UDPRXC_NR],
+ * ACCUMULATED, may be NULL: the six verdicts (per call they sum to m), BYTES
+ * (the sum of copy_len) and POLLINS.  Frames are addressed as gcl_l4_payload
+ * addresses them.
+ *
+ * Guarantee: no content of frames, offs, pkt_len, order, sock, l4_status or
+ * usock causes a read outside frames[0, frames_len) or the given arrays
+ * (order[0, m), the n-element per-packet arrays, usock[0, nsock)), or a write
+ * outside the m-element outputs, out_sock[0, nsock), rec_off[0, nsock],
+ * sock_off[0, nsock], counts and the workspace.
+ *
+ * What stays with the runtime: inq_lock and writing inq_len back (usock must
+ * be a snapshot no core changes meanwhile), linking the mbufs, the
+ * waitq_signals (ntaken) and poll_set (POLLIN), thread_create_with_buf and its
+ * failure drop for a spawner's datagrams, udp_conn_err, and the reads.
+ *
+ * gcl_udp_rx_workspace - bytes of device scratch a call takes for m entries,
+ *   nsock sockets and in->blocks = @blocks.  -EINVAL for a NULL @bytes,
+ *   m > 2^31, nsock > GCL_SOCK_MAX_ENTRIES or blocks > GCL_UDPRX_MAX_BLOCKS.
+ * gcl_udp_rx - asynchronous on @hip_stream: launches ordered by the stream
+ *   alone; no block waits for another and no atomic's order decides a result.
+ *   No allocation, no host synchronisation.  @workspace (device, 16-B aligned)
+ *   need not be zeroed and may be reused by the next call on the same stream.
+ *   m == 0 still writes out_sock, rec_off and sock_off.  -EINVAL for a NULL
+ *   ctx, b, in or out; a wrong in->size; a bad align; order == NULL with
+ *   m != b->n; m > 2^31; nsock > GCL_SOCK_MAX_ENTRIES; a NULL sock; with
+ *   nsock > 0 a NULL usock or out_sock; a NULL rec_off or sock_off; with m > 0
+ *   a NULL verdict, sflags, copy_len, dst_off, rec_idx or rec; any given array
+ *   that is not aligned to its element (usock, out_sock, rec: 16 B);
+ *   blocks > GCL_UDPRX_MAX_BLOCKS; a NULL workspace, one that is not 16-B
+ *   aligned or one smaller than gcl_udp_rx_workspace says; and, when m > 0,
+ *   what gcl_l4_payload refuses of a batch.  -EIO when a launch fails.
+ */
+/* verdict[j], and the first six counter slots */
+#define GCL_UDPRX_QUEUED 0
+#define GCL_UDPRX_SPAWN  1
+#define GCL_UDPRX_FULL   2
+#define GCL_UDPRX_CLOSED 3
+#define GCL_UDPRX_NOSOCK 4
+#define GCL_UDPRX_NA     5
+#define GCL_UDPRX_NR_VERDICTS 6
+#define GCL_UDPRX_MAX_BLOCKS 1024  /* the cap on in->blocks */
+enum { GCL_UDPRXC_BYTES = 6, GCL_UDPRXC_POLLINS = 7, GCL_UDPRXC_NR = 8 };
+/* sflags[j] and gcl_udp_sock_out.flags */
+#define GCL_UDPRX_SF_POLLIN 0x01   /* poll_set(&c->poll_src, POLLIN) */
+/* gcl_udp_sock.flags */
+#define GCL_UDPS_SHUTDOWN 0x01     /* c->shutdown */
+#define GCL_UDPS_ERR      0x02     /* c->inq_err != 0 */
+#define GCL_UDPS_SPAWNER  0x04     /* the entry is a udpspawner_t */
+struct gcl_udp_sock {      /* 16 B, 16-B aligned, host order: what udp_conn_recv reads */
+	int32_t inq_len, inq_cap;
+	uint8_t flags;         /* GCL_UDPS_* */
+	uint8_t pad[7];
+};
+struct gcl_udp_sock_out {  /* 16 B, 16-B aligned */
+	int32_t  inq_len;      /* after the list */
+	uint32_t ntaken;       /* QUEUED or SPAWN */
+	uint32_t ndropped;     /* FULL + CLOSED */
+	uint8_t  flags;        /* GCL_UDPRX_SF_POLLIN */
+	uint8_t  pad[3];       /* written as 0 */
+};
+struct gcl_udp_rec {       /* 16 B, 16-B aligned, host order: one taken datagram */
+	uint64_t dst_off;
+	uint32_t rip;
+	uint16_t rport, len;
+};
+struct gcl_udprx_in {
+	uint32_t size, align;            /* sizeof(struct gcl_udprx_in); align as in gcl_pay_in */
+	const uint32_t *order;           /* optional u32[m]; NULL: m == b->n and i = j */
+	uint64_t m;                      /* list entries, <= 2^31 */
+	const uint32_t *sock;            /* REQUIRED u32[n], as gcl_sock_lookup wrote it */
+	const uint8_t  *l4_status;       /* optional u8[n], as GCL_L4_VERIFY wrote it */
+	const struct gcl_udp_sock *usock; /* [nsock] */
+	uint32_t nsock;                  /* <= GCL_SOCK_MAX_ENTRIES */
+	uint32_t sock_base;              /* the cookie of usock[0] */
+	uint32_t blocks;                 /* 0: the library's choice; else the number of contiguous
+	                                    list ranges the grouping is cut into (tests) */
+	uint32_t pad;
+};
+struct gcl_udprx_out {               /* device, aligned to their element */
+	uint8_t  *verdict, *sflags;      /* [m] */
+	uint16_t *copy_len;              /* [m] */
+	uint64_t *dst_off;               /* [m] */
+	uint32_t *rec_idx;               /* [m] */
+	struct gcl_udp_rec *rec;         /* [m]; rec_off[nsock] of them are written */
+	struct gcl_udp_sock_out *out_sock; /* [nsock] */
+	uint32_t *rec_off;               /* u32[nsock + 1] */
+	uint64_t *sock_off;              /* u64[nsock + 1] */
+};
+int gcl_udp_rx_workspace(uint64_t m, uint32_t nsock, uint32_t blocks, size_t *bytes);
+int gcl_udp_rx(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct gcl_udprx_in *in,
+               const struct gcl_udprx_out *out, uint64_t *counts,
+               void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
