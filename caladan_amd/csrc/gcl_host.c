@@ -16,6 +16,7 @@
 #include "gcl_tcprxo.h"
 #include "gcl_tcprxs.h"
 #include "gcl_tcpopen.h"
+#include "gcl_tcpread.h"
 #include "gcl_tcptmr.h"
 #include "gcl_txq.h"
 #include "gcl_txh.h"
@@ -1936,6 +1937,136 @@ int gcl_tcp_txq_host(const struct gcl_txq_in *in, const struct gcl_txq_out *out,
 	out->totals[2] = c[GCL_TXQC_BYTES];
 	if (counts)
 		for (int i = 0; i < GCL_TXQC_NR; i++)
+			counts[i] += c[i];
+	return 0;
+}
+
+/* The rule of gcl_tcp_read (gclassify.h) on the CPU, one connection after the
+ * other: the walks of gcl_tcpread.h, then copy_into_iov's two cursors over the
+ * entries and the vectors for the items. */
+int gcl_tcp_read_host(const struct gcl_rd_in *in, const struct gcl_rd_out *out, uint64_t *counts)
+{
+	uint64_t c[GCL_RDC_NR] = {0}, items = 0, segs = 0, bytes = 0, retsum = 0;
+
+	if (!in || !out || in->size != sizeof(*in) ||
+	    ctl_refused(in->nconn, in->blocks, in->seg_cap, in->frame_stride, in->nconn, &out->seg, counts))
+		return -EINVAL;
+	const uint64_t nvec = in->voff ? in->nvec : 0;
+	if (in->nent > (1ull << 31) || nvec > (1ull << 31) || in->item_cap > (1ull << 31) || !out->totals)
+		return -EINVAL;
+	if (in->nconn && (!in->qoff || !in->rd || !in->conn || !in->addr || !out->out_conn))
+		return -EINVAL;
+	if ((in->nent && !in->ent) || (nvec && !in->iov))
+		return -EINVAL;
+	if (in->nconn && in->item_cap && (!out->src_off || !out->len || !out->dst_off || !out->item_conn ||
+	                                  !out->item_ent))
+		return -EINVAL;
+	if (((uintptr_t)in->qoff & 3) || ((uintptr_t)in->voff & 3) || ((uintptr_t)in->ent & 15) ||
+	    ((uintptr_t)in->iov & 15) || ((uintptr_t)in->rd & 15) || ((uintptr_t)in->conn & 15) ||
+	    ((uintptr_t)in->addr & 15) || ((uintptr_t)out->out_conn & 15) || ((uintptr_t)out->src_off & 7) ||
+	    ((uintptr_t)out->len & 1) || ((uintptr_t)out->dst_off & 7) || ((uintptr_t)out->item_conn & 3) ||
+	    ((uintptr_t)out->item_ent & 3) || ((uintptr_t)out->totals & 7))
+		return -EINVAL;
+
+	for (uint32_t j = 0; j < in->nconn; j++) {
+		const struct gcl_tcp_rd *rd = &in->rd[j];
+		const struct gcl_tcp_conn *cn = &in->conn[j];
+		const struct gcl_rd_iov one = {rd->dst_off, rd->len, {0}};
+		const struct gcl_rd_iov *iov = &one;
+		struct gcl_rd_res r;
+		uint32_t e0, v0 = 0, nv = 1, bad = 0, w[8], flags, written = 0;
+		const uint32_t n = gcl_rd_range(in->qoff[j], in->qoff[j + 1], in->nent, &e0, &bad);
+		const uint64_t first = items < in->item_cap ? items : in->item_cap;
+		uint64_t len = rd->len;
+
+		if (in->voff) {
+			nv = gcl_rd_range(in->voff[j], in->voff[j + 1], nvec, &v0, &bad);
+			iov = in->iov + v0;
+			len = 0;
+			for (uint32_t i = 0; i < nv; i++) /* iov_len() */
+				len += iov[i].len;
+		}
+		if (bad)
+			nv = 0;
+		if (gcl_rd_wait(rd->flags, n, rd->err, bad, cn->rcv_wnd, &r)) {
+			if (rd->flags & GCL_RD_PEEK) {
+				gcl_rd_peek_done(&r, gcl_rd_peek_walk(in->ent, e0, n, len));
+			} else {
+				uint32_t npop, pull;
+				int closed;
+				const uint64_t readlen = gcl_rd_walk(in->ent, e0, n, len, &npop, &pull, &closed);
+
+				gcl_rd_read_done(&r, readlen, npop, pull, closed, n, cn->rcv_nxt, rd->tx_last_ack,
+				                 rd->tx_last_win, rd->winmax);
+			}
+		}
+		flags = r.flags;
+		if (r.status == GCL_RDS_DONE && r.ret > 0) { /* a CLOSED connection's -err is no length */
+			/* copy_into_iov (tcp.c:1144-1181): entry i from @ea, vector v from @vb, the stream at @at */
+			const uint64_t ret = (uint64_t)r.ret;
+			uint64_t at = 0, ea = 0, vb = 0;
+			uint32_t i = 0, v = 0;
+
+			for (;;) {
+				const struct gcl_rdq_ent *m = &in->ent[e0 + i];
+				const uint64_t ee = ea + m->len < ret ? ea + m->len : ret;
+				const uint64_t ve = vb + iov[v].len < ret ? vb + iov[v].len : ret;
+				const uint64_t to = ee < ve ? ee : ve;
+				const uint64_t k = items + r.nitems;
+
+				if (k < in->item_cap) {
+					gcl_rd_item_store(out, k, j, e0 + i, m->off, ea, iov[v].off, vb, at, to);
+					written++;
+					bytes += to - at;
+				}
+				r.nitems++;
+				at = to;
+				/* the one that ends here goes on; at a tie the entry first; neither past the byte @ret */
+				if (ea + m->len <= vb + iov[v].len && ea + m->len < ret) {
+					ea += m->len;
+					i++;
+				} else if (vb + iov[v].len < ret) {
+					vb += iov[v].len;
+					v++;
+				} else {
+					break;
+				}
+			}
+			if (written < r.nitems)
+				flags |= GCL_RDO_ITEM_NOSPACE;
+			retsum += ret;
+		}
+		if (flags & GCL_RDO_ACK) {
+			if (ctl_emit(&out->seg, segs, in->seg_cap, in->frame_base, in->frame_stride, cn, &in->addr[j], j,
+			             GCL_CTL_ACK, j, cn->rcv_nxt, r.rcv_wnd))
+				c[GCL_RDC_ACKS]++;
+			else
+				flags |= GCL_RDO_SEG_NOSPACE;
+			segs++;
+		}
+		items += r.nitems;
+		gcl_rd_conn_words(&r, (uint32_t)first, written, flags, w);
+		memcpy(&out->out_conn[j], w, sizeof(w)); /* little-endian host */
+		c[GCL_RDC_DONE] += r.status == GCL_RDS_DONE;
+		c[GCL_RDC_AGAIN] += r.status == GCL_RDS_AGAIN;
+		c[GCL_RDC_BLOCK] += r.status == GCL_RDS_BLOCK;
+		c[GCL_RDC_CLOSED] += r.status == GCL_RDS_CLOSED;
+		c[GCL_RDC_PEEKS] += r.status == GCL_RDS_DONE && (rd->flags & GCL_RD_PEEK);
+		c[GCL_RDC_POPPED] += r.npop;
+		c[GCL_RDC_PARTIAL] += (flags & GCL_RDO_PARTIAL) ? 1 : 0;
+		c[GCL_RDC_RX_CLOSED] += (flags & GCL_RDO_RX_CLOSED) ? 1 : 0;
+		c[GCL_RDC_ITEMS] += written;
+		c[GCL_RDC_NOSPACE] += (flags & (GCL_RDO_SEG_NOSPACE | GCL_RDO_ITEM_NOSPACE)) ? 1 : 0;
+	}
+	c[GCL_RDC_BYTES] = bytes;
+	out->totals[0] = items;
+	out->totals[1] = items < in->item_cap ? items : in->item_cap;
+	out->totals[2] = bytes;
+	out->totals[3] = retsum;
+	out->seg.totals[0] = segs;
+	out->seg.totals[1] = segs < in->seg_cap ? segs : in->seg_cap;
+	if (counts)
+		for (int i = 0; i < GCL_RDC_NR; i++)
 			counts[i] += c[i];
 	return 0;
 }

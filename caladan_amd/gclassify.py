@@ -206,6 +206,24 @@ TXQC_NR, TXQ_MAX_BLOCKS, TXQ_MAX_CONN = 8, 1024, 1 << 20
 # its launches (csrc/gcl_txq.hip): connections per tile, and the queue length from which the
 # whole wave walks a queue
 TXQ_TILE, TXQ_LONG = 256, 64
+# gcl_tcp_read: the read's flags, the entry flag, the status byte, the connection flags, the
+# counters, the caps, its launches' tile, and struct gcl_tcp_rd, gcl_rdq_ent, gcl_rd_iov and
+# gcl_rd_conn_out
+RD_WANT, RD_PEEK, RD_NONBLOCK, RD_RX_CLOSED, RD_RX_EXCL = 0x01, 0x02, 0x04, 0x08, 0x10
+RDQE_FIN = 0x01
+RDS_NONE, RDS_DONE, RDS_AGAIN, RDS_BLOCK, RDS_CLOSED, RDS_BADRANGE = range(6)
+(RDO_RXWAKE, RDO_EXCL_LEFT, RDO_RX_CLOSED, RDO_PARTIAL, RDO_ACK, RDO_POLLIN_CLEAR, RDO_SEG_NOSPACE,
+ RDO_ITEM_NOSPACE) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80
+(RDC_DONE, RDC_AGAIN, RDC_BLOCK, RDC_CLOSED, RDC_PEEKS, RDC_POPPED, RDC_PARTIAL, RDC_RX_CLOSED, RDC_ACKS,
+ RDC_ITEMS, RDC_BYTES, RDC_NOSPACE) = range(12)
+RDC_NR, RD_MAX_BLOCKS, RD_MAX_CONN, RD_TILE = 12, 1024, 1 << 20, 256
+TCP_RD_DTYPE = np.dtype([("dst_off", "<u8"), ("len", "<u4"), ("tx_last_ack", "<u4"), ("tx_last_win", "<u4"),
+                         ("winmax", "<u4"), ("err", "<i4"), ("flags", "u1"), ("pad", "u1", (3,))])
+RDQ_ENT_DTYPE = np.dtype([("off", "<u8"), ("len", "<u2"), ("flags", "u1"), ("pad", "u1", (5,))])
+RD_IOV_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("pad", "u1", (4,))])
+RD_CONN_OUT_DTYPE = np.dtype([("ret", "<i8"), ("npop", "<u4"), ("pull", "<u4"), ("rcv_wnd", "<u4"),
+                              ("first_item", "<u4"), ("nitems", "<u4"), ("status", "u1"), ("flags", "u1"),
+                              ("pad", "u1", (2,))])
 TXQ_ENT_DTYPE = np.dtype([("seg_seq", "<u4"), ("seg_end", "<u4"), ("ts", "<u8")])
 TXQ_COLD_DTYPE = np.dtype([("frame_off", "<u8"), ("tcp_flags", "u1"), ("tcp_off", "u1"), ("flags", "u1"),
                            ("pad", "u1", (5,))])
@@ -573,6 +591,28 @@ class GclTxqOut(ctypes.Structure):
     _fields_ = [(f, ctypes.c_void_p) for f in TXQ_OUT_FIELDS]
 
 
+class GclRdIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("qoff", ctypes.c_void_p),
+                ("ent", ctypes.c_void_p), ("nent", ctypes.c_uint64), ("voff", ctypes.c_void_p),
+                ("iov", ctypes.c_void_p), ("nvec", ctypes.c_uint64), ("rd", ctypes.c_void_p),
+                ("conn", ctypes.c_void_p), ("addr", ctypes.c_void_p), ("nconn", ctypes.c_uint32),
+                ("frame_stride", ctypes.c_uint32), ("item_cap", ctypes.c_uint64), ("seg_cap", ctypes.c_uint64),
+                ("frame_base", ctypes.c_uint64)]
+
+
+RD_ITEM_FIELDS = ("src_off", "len", "dst_off", "item_conn", "item_ent")
+# the control segments' fields of a Classifier.tcp_read `out` dict: gcl_rd_out.seg
+RD_SEG_FIELDS = CTLSEG_SEG_FIELDS + ("seg_totals",)
+RD_OUT_FIELDS = ("out_conn",) + RD_ITEM_FIELDS + ("totals",) + RD_SEG_FIELDS
+
+
+class GclRdOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in ("out_conn",) + RD_ITEM_FIELDS + ("totals",)] + [("seg", GclCtlsegOut)]
+
+
+assert ctypes.sizeof(GclRdIn) == 112 and ctypes.sizeof(GclRdOut) == 104
+assert TCP_RD_DTYPE.itemsize == 32 and RDQ_ENT_DTYPE.itemsize == 16 and RD_IOV_DTYPE.itemsize == 16
+assert RD_CONN_OUT_DTYPE.itemsize == 32
 assert ctypes.sizeof(GclTxqIn) == 96 and ctypes.sizeof(GclTxqOut) == 80
 assert ctypes.sizeof(GclUdprxIn) == 64 and ctypes.sizeof(GclUdprxOut) == 72
 assert UDP_SOCK_DTYPE.itemsize == 16 and UDP_SOCK_OUT_DTYPE.itemsize == 16 and UDP_REC_DTYPE.itemsize == 16
@@ -738,6 +778,10 @@ def _load():
         "gcl_tcp_txq": (i32, [vp, ctypes.POINTER(GclTxqIn), ctypes.POINTER(GclTxqOut), vp, vp,
                               ctypes.c_size_t, vp]),
         "gcl_tcp_txq_host": (i32, [ctypes.POINTER(GclTxqIn), ctypes.POINTER(GclTxqOut), vp]),
+        "gcl_tcp_read_workspace": (i32, [u32, u64, u64, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_read": (i32, [vp, ctypes.POINTER(GclRdIn), ctypes.POINTER(GclRdOut), vp, vp,
+                               ctypes.c_size_t, vp]),
+        "gcl_tcp_read_host": (i32, [ctypes.POINTER(GclRdIn), ctypes.POINTER(GclRdOut), vp]),
         "gcl_neigh_tbl_new": (vp, []),
         "gcl_neigh_tbl_free": (None, [vp]),
         "gcl_neigh_tbl_set": (i32, [vp, vp, u32]),
@@ -1805,6 +1849,80 @@ def tcp_txq_workspace(nconn, blocks=0):
     return need.value
 
 
+RD_OUT_WIDTH = {"src_off": 8, "len": 2, "dst_off": 8, "item_conn": 4, "item_ent": 4}
+
+
+def _rd_structs(qoff, ent, nent, voff, iov, nvec, rd, conn, addr, nconn, item_cap, seg_cap, frame_base,
+                frame_stride, blocks, out, counts):
+    """The two structs of gcl_tcp_read / gcl_tcp_read_host, sizes checked; @out
+    maps RD_OUT_FIELDS to buffers."""
+    for arr in (qoff, voff):
+        if arr is not None and _nbytes(arr) < 4 * (nconn + 1):
+            raise ValueError("qoff or voff shorter than nconn + 1")
+    for arr, w in ((rd, 32), (conn, 48), (addr, 16), (out["out_conn"], 32)):
+        if arr is not None and _nbytes(arr) < w * nconn:
+            raise ValueError("per-connection array too small")
+    if ent is not None and _nbytes(ent) < 16 * nent:
+        raise ValueError("ent shorter than nent")
+    if voff is not None and iov is not None and _nbytes(iov) < 16 * nvec:
+        raise ValueError("iov shorter than nvec")
+    for f in RD_ITEM_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < RD_OUT_WIDTH[f] * item_cap:
+            raise ValueError(f"{f}: per-item array shorter than item_cap")
+    for f in CTLSEG_SEG_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < CTLSEG_OUT_WIDTH[f] * seg_cap:
+            raise ValueError(f"{f}: per-segment array shorter than seg_cap")
+    if out["totals"] is not None and _nbytes(out["totals"]) < 32:
+        raise ValueError("totals too small")
+    if out["seg_totals"] is not None and _nbytes(out["seg_totals"]) < 16:
+        raise ValueError("seg_totals too small")
+    if counts is not None and _nbytes(counts) < 8 * RDC_NR:
+        raise ValueError("counts buffer too small")
+    rin = GclRdIn(size=ctypes.sizeof(GclRdIn), blocks=blocks, qoff=_ptr(qoff), ent=_ptr(ent), nent=nent,
+                  voff=_ptr(voff), iov=_ptr(iov), nvec=nvec, rd=_ptr(rd), conn=_ptr(conn), addr=_ptr(addr),
+                  nconn=nconn, frame_stride=frame_stride, item_cap=item_cap, seg_cap=seg_cap,
+                  frame_base=frame_base)
+    seg = GclCtlsegOut(**{f: _ptr(out[f]) for f in CTLSEG_SEG_FIELDS}, totals=_ptr(out["seg_totals"]))
+    return rin, GclRdOut(**{f: _ptr(out[f]) for f in ("out_conn",) + RD_ITEM_FIELDS + ("totals",)}, seg=seg)
+
+
+def tcp_read_host(qoff, ent, rd, conn, addr, item_cap, seg_cap, voff=None, iov=None, frame_stride=64,
+                  frame_base=0, nconn=None, nent=None, nvec=None, blocks=0, out=None, counts=None):
+    """gcl_tcp_read_host: the rule of Classifier.tcp_read on the CPU over numpy
+    arrays.  @qoff is a u32[nconn + 1] CSR over the RDQ_ENT_DTYPE array @ent,
+    @voff an optional one over the RD_IOV_DTYPE array @iov; @rd, @conn and
+    @addr are TCP_RD_DTYPE, TCP_CONN_DTYPE and TCP_ADDR_DTYPE arrays indexed by
+    cookie.  @out maps RD_OUT_FIELDS to arrays (RD_CONN_OUT_DTYPE[nconn]; per
+    item u64, u16, u64, u32, u32, each @item_cap long; totals u64[4]; per
+    segment TXH_DESC_DTYPE, u64, u32, u8, u32, each @seg_cap long; seg_totals
+    u64[2]); the ones left out are allocated.  @counts is a u64[RDC_NR],
+    accumulated.  Returns the dict."""
+    nconn = len(rd) if nconn is None else nconn
+    nent = len(ent) if nent is None else nent
+    nvec = (len(iov) if iov is not None else 0) if nvec is None else nvec
+    out = dict(out or {})
+    for f, dt, k in (("out_conn", RD_CONN_OUT_DTYPE, nconn), ("src_off", np.uint64, item_cap),
+                     ("len", np.uint16, item_cap), ("dst_off", np.uint64, item_cap),
+                     ("item_conn", np.uint32, item_cap), ("item_ent", np.uint32, item_cap), ("totals", np.uint64, 4),
+                     ("desc", TXH_DESC_DTYPE, seg_cap), ("frame_off", np.uint64, seg_cap),
+                     ("seg_conn", np.uint32, seg_cap), ("seg_kind", np.uint8, seg_cap),
+                     ("seg_src", np.uint32, seg_cap), ("seg_totals", np.uint64, 2)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    rin, rout = _rd_structs(qoff, ent, nent, voff, iov, nvec, rd, conn, addr, nconn, item_cap, seg_cap, frame_base,
+                            frame_stride, blocks, out, counts)
+    _check(lib.gcl_tcp_read_host(ctypes.byref(rin), ctypes.byref(rout), _ptr(counts)), "gcl_tcp_read_host")
+    return out
+
+
+def tcp_read_workspace(nconn, nent, nvec=0, blocks=0):
+    """gcl_tcp_read_workspace: bytes of device scratch a call over @nconn connections, @nent queue
+    entries and @nvec vectors takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_read_workspace(nconn, nent, nvec, blocks, ctypes.byref(need)), "gcl_tcp_read_workspace")
+    return need.value
+
+
 def runtime_ip(r: int) -> int:
     return lib.gcl_runtime_ip(r)
 
@@ -2717,6 +2835,49 @@ class Classifier:
                 ws = self._txq_ws_buf = torch.empty(need, dtype=torch.uint8, device=out["totals"].device)
         _check(lib.gcl_tcp_txq(self._ctx, ctypes.byref(qin), ctypes.byref(qout), _ptr(counts), _ptr(ws),
                                _nbytes(ws), stream), "gcl_tcp_txq")
+        return out
+
+    def tcp_read(self, qoff, ent, nent, rd, conn, addr, nconn, item_cap, seg_cap, voff=None, iov=None, nvec=0,
+                 frame_stride=64, frame_base=0, blocks=0, out=None, counts=None, workspace=None, stream=None):
+        """gcl_tcp_read: tcp_read / tcp_readv on one runtime's @nconn
+        connections on the GPU, asynchronous: what each read returns, what it
+        takes off the receive queue, the copy items into the application's
+        buffers and the window-update ACKs.  @qoff is a device int32[nconn + 1]
+        CSR over @ent, device uint8[nent, 16] of RDQ_ENT_DTYPE records; @voff
+        and @iov (uint8[nvec, 16], RD_IOV_DTYPE) the optional vectors; @rd,
+        @conn and @addr are device uint8[nconn, 32 / 48 / 16] (16-B aligned).
+        @out maps RD_OUT_FIELDS to device buffers; the ones left out are
+        allocated on @qoff's device (out_conn uint8[nconn, 32]; src_off and
+        dst_off int64, len int16, item_conn and item_ent int32, item_cap long;
+        totals int64[4]; desc uint8[seg_cap, 32], frame_off int64, seg_conn and
+        seg_src int32, seg_kind uint8; seg_totals int64[2]).  @counts is a
+        device u64[RDC_NR], accumulated.  The scratch is @workspace, or a torch
+        tensor the classifier keeps for this call alone.  Returns the dict:
+        src_off, len and dst_off are copy_batch's with totals[1] their n, desc
+        and frame_off tx_hdr's with seg_totals[1] their m."""
+        import torch
+        dev = qoff.device if hasattr(qoff, "device") else None
+        out = dict(out or {})
+        ic, sc = max(item_cap, 1), max(seg_cap, 1)
+        for f, dt, shape in (("out_conn", torch.uint8, (max(nconn, 1), 32)), ("src_off", torch.int64, (ic,)),
+                             ("len", torch.int16, (ic,)), ("dst_off", torch.int64, (ic,)),
+                             ("item_conn", torch.int32, (ic,)), ("item_ent", torch.int32, (ic,)),
+                             ("totals", torch.int64, (4,)), ("desc", torch.uint8, (sc, 32)),
+                             ("frame_off", torch.int64, (sc,)), ("seg_conn", torch.int32, (sc,)),
+                             ("seg_kind", torch.uint8, (sc,)), ("seg_src", torch.int32, (sc,)),
+                             ("seg_totals", torch.int64, (2,))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        nvec = nvec if voff is not None else 0
+        rin, rout = _rd_structs(qoff, ent, nent, voff, iov, nvec, rd, conn, addr, nconn, item_cap, seg_cap,
+                                frame_base, frame_stride, blocks, out, counts)
+        ws = workspace
+        if ws is None:
+            need, ws = tcp_read_workspace(nconn, nent, nvec, blocks), getattr(self, "_rd_ws_buf", None)
+            if ws is None or ws.numel() < need or ws.device != out["totals"].device:
+                ws = self._rd_ws_buf = torch.empty(need, dtype=torch.uint8, device=out["totals"].device)
+        _check(lib.gcl_tcp_read(self._ctx, ctypes.byref(rin), ctypes.byref(rout), _ptr(counts), _ptr(ws),
+                                _nbytes(ws), stream), "gcl_tcp_read")
         return out
 
     def copy_batch(self, src, src_off, length, n, dst, dst_off=None, dst_stride=0, tx_olflags=None,

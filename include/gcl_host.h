@@ -362,6 +362,21 @@ int gcl_udp_rx_host(const struct gcl_batch *b, const struct gcl_udprx_in *in,
 int gcl_tcp_txq_host(const struct gcl_txq_in *in, const struct gcl_txq_out *out, uint64_t *counts);
 
 /*
+ * gcl_tcp_read_host - the rule of gcl_tcp_read (gclassify.h) on the CPU over
+ * host pointers, on one core: tcp_wait_rx, then tcp_read_wait's or
+ * tcp_read_wait_peek's loop over the connection's queue (runtime/net/tcp.c:
+ * 850-934, :963-988) taken literally, and copy_into_iov's two cursors
+ * (:1133-1185) for the copy items.  The GPU reaches the same numbers through
+ * prefix sums and searches, so the twin and the kernels check each other; the
+ * wait, the ACK test, the flags and an item's words are the inline code of
+ * csrc/gcl_tcpread.h that both run.  The same out_conn, items, segments and
+ * totals byte for byte, the same counts and the same guarantee.  in->blocks is
+ * checked and otherwise ignored.  0, or -EINVAL for what the call refuses (the
+ * ctx and the workspace apart).
+ */
+int gcl_tcp_read_host(const struct gcl_rd_in *in, const struct gcl_rd_out *out, uint64_t *counts);
+
+/*
  * gcl_host_deliver - consume @n verdicts in order.
  * @clients_by_id  dp.clients_by_id (iokernel/defs.h:386), @max_runtimes long
  * @clients        dp.clients[0..nr_clients) (broadcast order, rx.c:175)

@@ -3097,6 +3097,223 @@ int gcl_udp_rx(struct gcl_ctx *ctx, const struct gcl_batch *b, const struct gcl_
                const struct gcl_udprx_out *out, uint64_t *counts,
                void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/*
+ * The socket reads of TCP: the step between the receive chain and the
+ * application.  The gcl_tcp_rx* calls decide which segments a connection
+ * accepts and gcl_copy_batch leaves their bytes lying in sequence order;
+ * tcp_read / tcp_readv (runtime/net/tcp.c: tcp_wait_rx :850-876, tcp_read_wait
+ * :878-934, tcp_read_wait_peek :963-988, copy_mbufs_to_buf :1013-1038,
+ * copy_into_iov :1133-1185, tcp_conn_shutdown_rx :1492-1502) then take them
+ * off c->rxq into the application's buffer, give the window back and send the
+ * window-update ACK (tcp_tx_ack with __tcp_add_tcphdr's tx_last_ack and
+ * tx_last_win, tcp_out.c:59-61).  gcl_tcp_read does that for every connection
+ * of one runtime at one instant, on a snapshot:
+ *
+ *   gcl_tcp_rx* -> gcl_copy_batch -> (rxq) -> gcl_tcp_read -> gcl_copy_batch
+ *   (src_off, len, dst_off) ; the ACKs -> gcl_tx_hdr -> gcl_l4_csum GCL_L4_FILL
+ *
+ * It works on every context and touches no table.
+ *
+ * The receive queues come as a CSR like gcl_tcp_txq's: connection c owns
+ * entries [qoff[c], qoff[c + 1]) of ent in queue order; an entry says where
+ * the mbuf's data lies in the source region (off), mbuf_length (len) and
+ * GCL_RDQE_FIN for m->flags & TCP_FIN.  dst_off[j] and copy_len[j] of a
+ * gcl_tcp_rx* call become off and len directly.  The read of connection c is
+ * rd[c]: flags (GCL_RD_*), the words of the ACK test, c->err, and its buffer
+ * (dst_off, len).  With voff given the buffer is instead the vectors
+ * [voff[c], voff[c + 1]) of iov, the read's length L their summed len
+ * (iov_len()), and rd[c].dst_off and rd[c].len are ignored.  A range of qoff
+ * or voff that is inverted or not inside [0, nent] ([0, nvec]) makes the
+ * connection GCL_RDS_BADRANGE: it is not read, as if GCL_RD_WANT were clear.
+ *
+ * One connection; n is its queue's length, A_i the summed len of its first i
+ * entries, L the read's length:
+ *   1. no GCL_RD_WANT: status NONE, nothing changes.
+ *   2. tcp_wait_rx: not RX_CLOSED, and RX_EXCL or n == 0: with NONBLOCK status
+ *      AGAIN, ret -11 (-EAGAIN); else status BLOCK, ret 0 (the waitq_wait
+ *      stays with the runtime).  Nothing changes.
+ *   3. RX_CLOSED: status CLOSED, ret = -(int64_t)err, nothing changes.
+ *   4. GCL_RD_PEEK (tcp_read_wait_peek): ret = min(A_n, L); FIN flags are not
+ *      looked at, nothing is popped, rcv_wnd stays and no ACK is sent; the
+ *      bytes are copied (5d); GCL_RDO_RXWAKE (tcp_exclusive_finish).  With
+ *      ret == 0 the reference returns with rx_exclusive set and never clears
+ *      it: that case reports GCL_RDO_EXCL_LEFT instead of RXWAKE.  Status DONE.
+ *   5. tcp_read_wait, as the host twin walks it:
+ *      a. while readlen < L: take the top entry, with none stop.  With FIN:
+ *         tcp_conn_shutdown_rx (GCL_RDO_RX_CLOSED), and if its len is 0 stop,
+ *         the entry stays queued.  If L - readlen < len the entry is pulled by
+ *         pull = L - readlen (GCL_RDO_PARTIAL and RXWAKE), readlen = L, stop.
+ *         Otherwise pop it (npop) and add its len.
+ *      b. rcv_wnd += readlen (mod 2^32); GCL_RDO_ACK iff wraps_gte(rcv_nxt +
+ *         rcv_wnd, tx_last_ack + tx_last_win + winmax / 4), for L == 0 too.
+ *      c. GCL_RDO_POLLIN_CLEAR iff npop == n.
+ *      d. The copy items.  With ret > 0: ne is the smallest i >= 1 with A_i >=
+ *         ret, nv the same over the vectors' running sums B_j (without voff
+ *         the one vector (rd.dst_off, rd.len)).  The cuts are the multiset
+ *         {A_1..A_{ne-1}} + {B_1..B_{nv-1}}, sorted, an entry cut before an
+ *         equal vector cut; with 0 in front and ret behind they bound exactly
+ *         ne + nv - 1 items.  Item t spans [c_t, c_{t+1}) of the stream and
+ *         lies in entry i and vector j: src_off = ent.off + (c_t - A_i),
+ *         dst_off = iov.off + (c_t - B_j), len = c_{t+1} - c_t (it fits a
+ *         uint16_t: an item lies in one entry), item_conn = c, item_ent = the
+ *         entry's index in ent.  Coinciding cuts and zero-length entries and
+ *         vectors give len 0 items, which gcl_copy_batch passes over.  With
+ *         ret == 0 there are none.  A connection takes at most n + its vector
+ *         count, so item_cap = nent + max(nvec, nconn) always suffices.
+ *      e. status DONE, ret = readlen.
+ *    The kernels use 5a's closed form: z = the first zero-length FIN entry or
+ *    n; if A_z >= L, npop = the smallest i with A_i >= L and pull = 0, except
+ *    that with A_i > L npop = i - 1 and pull = L - A_{i-1}; else npop = z and
+ *    ret = A_z.  RX_CLOSED iff an entry examined as top has FIN: entries
+ *    0..npop-1, and entry npop when it exists and the walk did not end on
+ *    readlen >= L right after a pop.  L == 0 examines none.
+ *
+ * A connection with GCL_RDO_ACK emits one control segment (the rule of
+ * gcl_tcp_tick above), in connection order: tcp_flags 0x10, seq =
+ * conn[c].snd_nxt, ack = conn[c].rcv_nxt, win from rcv_wnd AFTER the read,
+ * seg_kind GCL_CTL_ACK, seg_src = seg_conn = c, frame_off = frame_base + k *
+ * frame_stride.  A written segment implies tx_last_ack = rcv_nxt and
+ * tx_last_win = the new rcv_wnd for the host to store.  A connection whose
+ * ACK lies at or past seg_cap gets GCL_RDO_SEG_NOSPACE; its other words
+ * change all the same, like the -ENOMEM of tcp_tx_ack.
+ *
+ * out_conn[c], every byte written: ret; npop and pull (the host pops npop
+ * entries and pulls pull bytes off the next: mbuf_pull, seg_seq += pull);
+ * rcv_wnd after the read; first_item = min(the items wanted by the
+ * connections before it, item_cap); nitems, the items written for it; status;
+ * flags.  Per item k < min(wanted, item_cap), in connection order and then
+ * stream order: src_off, len, dst_off (the types gcl_copy_batch takes),
+ * item_conn, item_ent; items at and past item_cap are not written and the
+ * connection gets GCL_RDO_ITEM_NOSPACE.  totals u64[4]: items wanted, items
+ * written, the bytes of the written items, the sum of the DONE connections'
+ * ret (a CLOSED connection's -err is no length, whatever its sign).
+ * seg.totals u64[2] as for every control-segment call.
+ *
+ * @counts is a device u64[GCL_RDC_NR], ACCUMULATED, may be NULL: DONE, AGAIN,
+ * BLOCK and CLOSED connections, PEEKS, POPPED entries, PARTIAL and RX_CLOSED
+ * connections, ACKS written, ITEMS written, their BYTES, and NOSPACE
+ * connections (either NOSPACE flag).
+ *
+ * Every pointer is a device pointer; each array is aligned to its element,
+ * conn, addr, rd, ent, iov, out_conn and desc to 16 B.  Asynchronous on
+ * @hip_stream: launches ordered by the stream alone (two three-launch prefix
+ * scans over ent and iov, decide, the scan of the block sums, emit); no block
+ * waits for another, no launch walks a connection's queue serially, and no
+ * atomic hands out a position: atomics only add to counts and totals.  No
+ * allocation, no host synchronisation.  @workspace (device, 16-B aligned) need
+ * not be zeroed and may be reused by the next call on the same stream.
+ * nconn == 0 still writes both totals.
+ *
+ * Guarantee: no content of qoff, ent, voff, iov, rd, conn or addr causes a
+ * read outside the given arrays, or a write outside the first item_cap
+ * elements of the per-item outputs, the first seg_cap elements of the
+ * per-segment outputs, out_conn[0, nconn), both totals, counts and the
+ * workspace.  Garbage qoff and voff are included: decreasing values, or values
+ * past nent or nvec.  Ranges that overlap are each read.
+ *
+ * What stays with the runtime: the connection lock and waitq_wait (BLOCK), the
+ * waitq_releases and poll_set / poll_clear themselves, mbuf_list_free, and
+ * writing rcv_wnd, tx_last_ack, tx_last_win, rx_exclusive and rx_closed back.
+ *
+ * gcl_tcp_read_workspace - bytes of device scratch a call takes: 16 per queue
+ *   entry and 8 per vector plus a fixed part.  -EINVAL for a NULL @bytes,
+ *   nconn > 2^20, nent or nvec > 2^31 or blocks > GCL_RD_MAX_BLOCKS.
+ * gcl_tcp_read - -EINVAL for a NULL ctx, in or out; a wrong in->size; nconn >
+ *   2^20; nent, nvec, item_cap or seg_cap > 2^31; blocks > GCL_RD_MAX_BLOCKS;
+ *   frame_stride < 54; a NULL totals or seg.totals; with nconn > 0 a NULL qoff,
+ *   rd, conn, addr or out_conn; with nent > 0 a NULL ent; with voff and nvec > 0
+ *   a NULL iov (without voff neither iov nor nvec is looked at); with nconn > 0 and item_cap > 0 a NULL per-item output; with
+ *   nconn > 0 and seg_cap > 0 a NULL per-segment output; any given array that
+ *   is not aligned to its element; a NULL workspace, one that is not 16-B
+ *   aligned or one smaller than gcl_tcp_read_workspace says.  -EIO when a
+ *   launch fails.
+ */
+/* gcl_tcp_rd.flags */
+#define GCL_RD_WANT       0x01  /* a read is issued on this connection */
+#define GCL_RD_PEEK       0x02
+#define GCL_RD_NONBLOCK   0x04  /* the call's or c->nonblocking */
+#define GCL_RD_RX_CLOSED  0x08  /* c->rx_closed */
+#define GCL_RD_RX_EXCL    0x10  /* c->rx_exclusive */
+/* gcl_rdq_ent.flags */
+#define GCL_RDQE_FIN      0x01  /* m->flags & TCP_FIN */
+/* gcl_rd_conn_out.status */
+#define GCL_RDS_NONE      0
+#define GCL_RDS_DONE      1
+#define GCL_RDS_AGAIN     2
+#define GCL_RDS_BLOCK     3
+#define GCL_RDS_CLOSED    4
+#define GCL_RDS_BADRANGE  5
+/* gcl_rd_conn_out.flags */
+#define GCL_RDO_RXWAKE        0x01  /* tcp_exclusive_finish: rx_exclusive = false, release rx_wq */
+#define GCL_RDO_EXCL_LEFT     0x02  /* a peek of 0 bytes: rx_exclusive stays set */
+#define GCL_RDO_RX_CLOSED     0x04  /* tcp_conn_shutdown_rx: rx_closed, POLLRDHUP | POLLIN, release rx_wq */
+#define GCL_RDO_PARTIAL       0x08  /* entry npop is pulled by `pull` bytes */
+#define GCL_RDO_ACK           0x10  /* tcp_tx_ack */
+#define GCL_RDO_POLLIN_CLEAR  0x20  /* poll_clear(&c->poll_src, POLLIN) */
+#define GCL_RDO_SEG_NOSPACE   0x40  /* its ACK lay at or past seg_cap */
+#define GCL_RDO_ITEM_NOSPACE  0x80  /* an item of it lay at or past item_cap */
+#define GCL_RD_MAX_BLOCKS 1024      /* the cap on in->blocks */
+#define GCL_RD_MAX_CONN (1u << 20)
+enum { GCL_RDC_DONE = 0, GCL_RDC_AGAIN, GCL_RDC_BLOCK, GCL_RDC_CLOSED, GCL_RDC_PEEKS, GCL_RDC_POPPED,
+       GCL_RDC_PARTIAL, GCL_RDC_RX_CLOSED, GCL_RDC_ACKS, GCL_RDC_ITEMS, GCL_RDC_BYTES, GCL_RDC_NOSPACE,
+       GCL_RDC_NR = 12 };
+struct gcl_tcp_rd {        /* 32 B, 16-B aligned, host order: one read and what the ACK test reads */
+	uint64_t dst_off;      /* without voff: the buffer */
+	uint32_t len;
+	uint32_t tx_last_ack, tx_last_win, winmax;
+	int32_t  err;          /* c->err */
+	uint8_t  flags;        /* GCL_RD_* */
+	uint8_t  pad[3];
+};
+struct gcl_rdq_ent {       /* 16 B: one mbuf of c->rxq */
+	uint64_t off;          /* where its data lies in the source region */
+	uint16_t len;          /* mbuf_length */
+	uint8_t  flags;        /* GCL_RDQE_* */
+	uint8_t  pad[5];
+};
+struct gcl_rd_iov {        /* 16 B: one struct iovec */
+	uint64_t off;
+	uint32_t len;
+	uint8_t  pad[4];
+};
+struct gcl_rd_conn_out {   /* 32 B, 16-B aligned */
+	int64_t  ret;
+	uint32_t npop, pull, rcv_wnd, first_item, nitems;
+	uint8_t  status;       /* GCL_RDS_* */
+	uint8_t  flags;        /* GCL_RDO_* */
+	uint8_t  pad[2];       /* written as 0 */
+};
+struct gcl_rd_in {
+	uint32_t size, blocks;             /* sizeof(struct gcl_rd_in); blocks as in gcl_tick_in: the ranges of
+	                                      every scan and sweep of the call */
+	const uint32_t *qoff;              /* u32[nconn + 1] */
+	const struct gcl_rdq_ent *ent;     /* [nent] */
+	uint64_t nent;                     /* <= 2^31 */
+	const uint32_t *voff;              /* optional u32[nconn + 1] */
+	const struct gcl_rd_iov *iov;      /* [nvec] */
+	uint64_t nvec;                     /* <= 2^31; not looked at without voff */
+	const struct gcl_tcp_rd *rd;       /* [nconn] */
+	const struct gcl_tcp_conn *conn;   /* [nconn]: rcv_nxt, rcv_wnd and snd_nxt are read */
+	const struct gcl_tcp_addr *addr;   /* [nconn] */
+	uint32_t nconn;                    /* <= 2^20 */
+	uint32_t frame_stride;             /* bytes, >= GCL_CTL_MIN_STRIDE */
+	uint64_t item_cap;                 /* <= 2^31: the length of every per-item output array */
+	uint64_t seg_cap;                  /* <= 2^31: the length of every per-segment output array */
+	uint64_t frame_base;
+};
+struct gcl_rd_out {                    /* device, aligned to their element */
+	struct gcl_rd_conn_out *out_conn;  /* [nconn] */
+	uint64_t *src_off;                 /* [item_cap] */
+	uint16_t *len;                     /* [item_cap] */
+	uint64_t *dst_off;                 /* [item_cap] */
+	uint32_t *item_conn, *item_ent;    /* [item_cap] */
+	uint64_t *totals;                  /* u64[4], required: items wanted, written, their bytes, bytes read */
+	struct gcl_ctlseg_out seg;         /* the ACKs; seg.totals required */
+};
+int gcl_tcp_read_workspace(uint32_t nconn, uint64_t nent, uint64_t nvec, uint32_t blocks, size_t *bytes);
+int gcl_tcp_read(struct gcl_ctx *ctx, const struct gcl_rd_in *in, const struct gcl_rd_out *out,
+                 uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
