@@ -17,6 +17,7 @@
 #include "gcl_tcprxs.h"
 #include "gcl_tcpopen.h"
 #include "gcl_tcpread.h"
+#include "gcl_tcpwrite.h"
 #include "gcl_tcptmr.h"
 #include "gcl_txq.h"
 #include "gcl_txh.h"
@@ -2068,6 +2069,207 @@ int gcl_tcp_read_host(const struct gcl_rd_in *in, const struct gcl_rd_out *out, 
 	if (counts)
 		for (int i = 0; i < GCL_RDC_NR; i++)
 			counts[i] += c[i];
+	return 0;
+}
+
+/* the mbuf tcp_tx_send works on, and c->tx_pending */
+struct wr_mbuf {
+	uint64_t frame_off;
+	uint32_t seg_seq, fill;
+	int live;
+};
+
+/* one connection's write as it runs */
+struct wr_run {
+	struct wr_mbuf pend;
+	uint32_t snd_nxt, mss;
+	uint32_t segs, items, slots, shorts, pushes;
+};
+
+/* tcp_tx_send (tcp_out.c:313-386) over @len bytes at @src for connection @c, whose segments, items and
+ * slots start at @S, @I and @K of the call; with @emit it writes them */
+static void wr_tx_send(const struct gcl_wr_in *in, const struct gcl_wr_out *out, int emit, struct wr_run *r,
+                       uint32_t c, uint64_t S, uint64_t I, uint64_t K, uint64_t src, uint32_t len, int push)
+{
+	const struct gcl_tcp_conn *cn = &in->conn[c];
+	uint32_t pos = 0;
+
+	do {
+		struct wr_mbuf m;
+		uint32_t seglen;
+
+		if (r->pend.live) { /* :331 */
+			m = r->pend;
+			r->pend.live = 0;
+			seglen = len - pos < r->mss - m.fill ? len - pos : r->mss - m.fill;
+		} else {
+			seglen = len - pos < r->mss ? len - pos : r->mss;
+			m.seg_seq = r->snd_nxt;
+			m.fill = 0;
+			m.frame_off = in->frame_base + (K + r->slots) * in->frame_stride;
+			m.live = 1;
+			r->slots++;
+		}
+		if (emit) { /* memcpy(mbuf_put(m, seglen), pos, seglen) */
+			const uint64_t k = I + r->items;
+			out->src_off[k] = src + pos;
+			out->len[k] = (uint16_t)seglen;
+			out->dst_off[k] = m.frame_off + GCL_WR_HDR + m.fill;
+			out->item_conn[k] = c;
+			out->item_seg[k] = (uint32_t)(S + r->segs);
+		}
+		r->items++;
+		m.fill += seglen;
+		r->snd_nxt += seglen;
+		pos += seglen;
+		if (!push && pos == len && (size_t)m.fill - GCL_WR_TCPHDR < r->mss) { /* :359: mbuf_length has no header yet */
+			r->pend = m;
+			break;
+		}
+		if (!push && pos == len)
+			r->shorts++;
+		if (emit) {
+			const uint64_t k = S + r->segs;
+			uint32_t a[4], d[16];
+
+			memcpy(a, &in->addr[c], sizeof(a));
+			gcl_wr_seg_words(a, in->wr[c].ecn, GCL_WR_TCP_ACK | (push && pos == len ? GCL_WR_TCP_PUSH : 0), m.seg_seq,
+			                 cn->rcv_nxt, cn->rcv_wnd, m.fill, m.frame_off, in->now, d);
+			memcpy(&out->desc[k], d, 32); /* little-endian host */
+			memcpy(&out->txq_ent[k], d + 8, 16);
+			memcpy(&out->txq_cold[k], d + 12, 16);
+			out->frame_off[k] = m.frame_off;
+			out->seg_conn[k] = c;
+		}
+		r->segs++;
+		r->pushes += push && pos == len;
+	} while (pos < len);
+}
+
+/* tcp_write3's or tcp_writev2's sends (tcp.c:1374, :1405-1416) for connection @c */
+static void wr_run_conn(const struct gcl_wr_in *in, const struct gcl_wr_out *out, int emit, struct wr_run *r,
+                        uint32_t c, uint64_t S, uint64_t I, uint64_t K, uint32_t v0, uint32_t nv, uint32_t winlen)
+{
+	const struct gcl_tcp_wr *wr = &in->wr[c];
+
+	memset(r, 0, sizeof(*r));
+	r->snd_nxt = in->conn[c].snd_nxt;
+	r->mss = wr->snd_mss;
+	if (wr->pend_len) {
+		r->pend.live = 1;
+		r->pend.fill = wr->pend_len;
+		r->pend.seg_seq = r->snd_nxt - wr->pend_len;
+		r->pend.frame_off = wr->pend_frame_off;
+	}
+	if (!(wr->flags & GCL_WR_VEC)) {
+		wr_tx_send(in, out, emit, r, c, S, I, K, wr->src_off, wr->len < winlen ? wr->len : winlen, 1);
+		return;
+	}
+	for (uint32_t i = 0; i < nv; i++) {
+		const struct gcl_rd_iov *v = &in->iov[v0 + i];
+
+		if (winlen == 0)
+			break;
+		if (!v->len)
+			continue;
+		const uint32_t x = v->len < winlen ? v->len : winlen;
+		wr_tx_send(in, out, emit, r, c, S, I, K, v->off, x, i == nv - 1 && v->len <= winlen);
+		winlen -= x;
+	}
+}
+
+/* The rule of gcl_tcp_write (gclassify.h) on the CPU, one connection after the
+ * other: the wait of gcl_tcpwrite.h, then the reference's loops, run once to
+ * count and, when everything fits, once more to write. */
+int gcl_tcp_write_host(const struct gcl_wr_in *in, const struct gcl_wr_out *out, uint64_t *counts)
+{
+	uint64_t cnt[GCL_WRC_NR] = {0}, S = 0, I = 0, K = 0, named = 0, tot[6] = {0};
+
+	if (!in || !out || in->size != sizeof(*in) || in->nconn > GCL_WR_MAX_CONN || in->blocks > GCL_WR_MAX_BLOCKS ||
+	    in->seg_cap > (1ull << 31) || in->item_cap > (1ull << 31) || in->frame_stride < GCL_WR_HDR ||
+	    in->frame_stride > GCL_WR_MAX_STRIDE || !out->totals)
+		return -EINVAL;
+	const uint64_t nvec = in->voff ? in->nvec : 0;
+	if (nvec > (1ull << 31))
+		return -EINVAL;
+	if (in->nconn && (!in->wr || !in->conn || !in->addr || !out->out_conn))
+		return -EINVAL;
+	if (nvec && !in->iov)
+		return -EINVAL;
+	if (in->nconn && in->seg_cap && (!out->desc || !out->frame_off || !out->seg_conn || !out->txq_ent || !out->txq_cold))
+		return -EINVAL;
+	if (in->nconn && in->item_cap && (!out->src_off || !out->len || !out->dst_off || !out->item_conn || !out->item_seg))
+		return -EINVAL;
+	if (((uintptr_t)in->voff & 3) || ((uintptr_t)in->iov & 15) || ((uintptr_t)in->wr & 15) ||
+	    ((uintptr_t)in->conn & 15) || ((uintptr_t)in->addr & 15) || ((uintptr_t)out->out_conn & 15) ||
+	    ((uintptr_t)out->desc & 15) || ((uintptr_t)out->frame_off & 7) || ((uintptr_t)out->seg_conn & 3) ||
+	    ((uintptr_t)out->txq_ent & 15) || ((uintptr_t)out->txq_cold & 15) || ((uintptr_t)out->src_off & 7) ||
+	    ((uintptr_t)out->len & 1) || ((uintptr_t)out->dst_off & 7) || ((uintptr_t)out->item_conn & 3) ||
+	    ((uintptr_t)out->item_seg & 3) || ((uintptr_t)out->totals & 7) || ((uintptr_t)counts & 7))
+		return -EINVAL;
+	const uint64_t slot_cap = gcl_wr_slot_cap(in->frames_len, in->frame_base, in->frame_stride);
+
+	for (uint32_t c = 0; c < in->nconn; c++) {
+		const struct gcl_tcp_wr *wr = &in->wr[c];
+		const struct gcl_tcp_conn *cn = &in->conn[c];
+		const uint32_t fseg = (uint32_t)(S < in->seg_cap ? S : in->seg_cap);
+		const uint32_t fitem = (uint32_t)(I < in->item_cap ? I : in->item_cap);
+		uint32_t w[12], o[12], v0 = 0, nv = 0, bad = 0;
+		struct gcl_wr_res r;
+
+		memcpy(w, wr, sizeof(w)); /* little-endian host */
+		if (wr->flags & GCL_WR_VEC) {
+			nv = gcl_wr_range(in->voff, c, nvec, &v0, &bad);
+			if (named + nv > nvec) /* the rows the kernels' walk would take */
+				bad = 1;
+		}
+		named += gcl_wr_named(w, in->voff, c, nvec);
+		if (!gcl_wr_wait(w, bad, cn->snd_una, cn->snd_wnd, cn->snd_nxt, in->frame_stride, &r)) {
+			gcl_wr_conn_words(r.ret, cn->snd_nxt, fseg, 0, fitem, 0, wr->pend_len, wr->pend_frame_off, r.status,
+			                  r.flags, o);
+		} else {
+			struct wr_run run;
+
+			wr_run_conn(in, out, 0, &run, c, S, I, K, v0, nv, r.winlen);
+			if (gcl_wr_fits(S, run.segs, in->seg_cap, I, run.items, in->item_cap, K, run.slots, slot_cap)) {
+				const uint32_t taken = run.snd_nxt - cn->snd_nxt;
+
+				wr_run_conn(in, out, 1, &run, c, S, I, K, v0, nv, r.winlen);
+				if (run.pend.live) /* the items of the segment that stays held */
+					for (uint64_t k = I + run.items; k > I && out->item_seg[k - 1] == (uint32_t)(S + run.segs); k--)
+						out->item_seg[k - 1] = GCL_WR_SEG_HELD;
+				gcl_wr_conn_words(taken, run.snd_nxt, fseg, run.segs, fitem, run.items,
+				                  run.pend.live ? run.pend.fill : 0, run.pend.live ? run.pend.frame_off : 0, GCL_WRS_DONE,
+				                  gcl_wr_finish_flags(r.flags, run.segs, cn->rcv_nxt, wr->tx_last_ack, cn->snd_una,
+				                                      cn->snd_wnd, run.snd_nxt), o);
+				cnt[GCL_WRC_SEGS] += run.segs;
+				cnt[GCL_WRC_PUSH] += run.pushes;
+				cnt[GCL_WRC_HELD] += run.pend.live;
+				cnt[GCL_WRC_SHORT] += run.shorts;
+				cnt[GCL_WRC_ITEMS] += run.items;
+				cnt[GCL_WRC_BYTES] += taken;
+				tot[1] += run.segs;
+				tot[3] += run.items;
+				tot[4] += run.slots;
+				tot[5] += taken;
+			} else {
+				r.status = GCL_WRS_NOSPACE;
+				gcl_wr_conn_words(-GCL_WR_ENOBUFS, cn->snd_nxt, fseg, 0, fitem, 0, wr->pend_len, wr->pend_frame_off,
+				                  r.status, 0, o);
+			}
+			S += run.segs;
+			I += run.items;
+			K += run.slots;
+		}
+		memcpy(&out->out_conn[c], o, sizeof(o));
+		cnt[o[10] & 0xFFu]++;
+	}
+	tot[0] = S;
+	tot[2] = I;
+	memcpy(out->totals, tot, sizeof(tot));
+	if (counts)
+		for (int i = 0; i < GCL_WRC_NR; i++)
+			counts[i] += cnt[i];
 	return 0;
 }
 

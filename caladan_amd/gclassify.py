@@ -224,6 +224,20 @@ RD_IOV_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("pad", "u1", (4,))])
 RD_CONN_OUT_DTYPE = np.dtype([("ret", "<i8"), ("npop", "<u4"), ("pull", "<u4"), ("rcv_wnd", "<u4"),
                               ("first_item", "<u4"), ("nitems", "<u4"), ("status", "u1"), ("flags", "u1"),
                               ("pad", "u1", (2,))])
+# gcl_tcp_write: the write's flags, the status byte (also the first counter slots), the connection
+# flags, the other counters, the caps, its launches' tile, and struct gcl_tcp_wr and gcl_wr_conn_out
+(WR_WANT, WR_VEC, WR_NONBLOCK, WR_NO_PARTIAL, WR_TX_CLOSED, WR_TX_EXCL, WR_ZERO_WND,
+ WR_BELOW_EST) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80
+WRS_NONE, WRS_DONE, WRS_AGAIN, WRS_BLOCK, WRS_CLOSED, WRS_NOSPC, WRS_REFUSED, WRS_NOSPACE = range(8)
+WRO_ZWND_ARM, WRO_ZWND_CLEAR, WRO_ACKS_RESET, WRO_TXWAKE, WRO_ACK_TS, WRO_POLLOUT_CLEAR = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+WRC_SEGS, WRC_PUSH, WRC_HELD, WRC_SHORT, WRC_ITEMS, WRC_BYTES = range(8, 14)
+WRC_NR, WR_MAX_IOV, WR_MAX_BLOCKS, WR_MAX_CONN, WR_TILE, WR_SEG_HELD = 14, 1024, 1024, 1 << 20, 256, 0xFFFFFFFF
+TCP_WR_DTYPE = np.dtype([("src_off", "<u8"), ("len", "<u4"), ("tx_last_ack", "<u4"), ("pend_frame_off", "<u8"),
+                         ("pend_len", "<u4"), ("err", "<i4"), ("snd_mss", "<u2"), ("ecn", "u1"), ("flags", "u1"),
+                         ("pad", "u1", (12,))])
+WR_CONN_OUT_DTYPE = np.dtype([("ret", "<i8"), ("snd_nxt", "<u4"), ("first_seg", "<u4"), ("nseg", "<u4"),
+                              ("first_item", "<u4"), ("nitems", "<u4"), ("pend_len", "<u4"),
+                              ("pend_frame_off", "<u8"), ("status", "u1"), ("flags", "u1"), ("pad", "u1", (6,))])
 TXQ_ENT_DTYPE = np.dtype([("seg_seq", "<u4"), ("seg_end", "<u4"), ("ts", "<u8")])
 TXQ_COLD_DTYPE = np.dtype([("frame_off", "<u8"), ("tcp_flags", "u1"), ("tcp_off", "u1"), ("flags", "u1"),
                            ("pad", "u1", (5,))])
@@ -610,6 +624,25 @@ class GclRdOut(ctypes.Structure):
     _fields_ = [(f, ctypes.c_void_p) for f in ("out_conn",) + RD_ITEM_FIELDS + ("totals",)] + [("seg", GclCtlsegOut)]
 
 
+class GclWrIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("now", ctypes.c_uint64),
+                ("voff", ctypes.c_void_p), ("iov", ctypes.c_void_p), ("nvec", ctypes.c_uint64),
+                ("wr", ctypes.c_void_p), ("conn", ctypes.c_void_p), ("addr", ctypes.c_void_p),
+                ("nconn", ctypes.c_uint32), ("frame_stride", ctypes.c_uint32), ("seg_cap", ctypes.c_uint64),
+                ("item_cap", ctypes.c_uint64), ("frame_base", ctypes.c_uint64), ("frames_len", ctypes.c_uint64)]
+
+
+WR_SEG_FIELDS = ("desc", "frame_off", "seg_conn", "txq_ent", "txq_cold")
+WR_ITEM_FIELDS = ("src_off", "len", "dst_off", "item_conn", "item_seg")
+WR_OUT_FIELDS = ("out_conn",) + WR_SEG_FIELDS + WR_ITEM_FIELDS + ("totals",)
+
+
+class GclWrOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in WR_OUT_FIELDS]
+
+
+assert ctypes.sizeof(GclWrIn) == 104 and ctypes.sizeof(GclWrOut) == 96
+assert TCP_WR_DTYPE.itemsize == 48 and WR_CONN_OUT_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclRdIn) == 112 and ctypes.sizeof(GclRdOut) == 104
 assert TCP_RD_DTYPE.itemsize == 32 and RDQ_ENT_DTYPE.itemsize == 16 and RD_IOV_DTYPE.itemsize == 16
 assert RD_CONN_OUT_DTYPE.itemsize == 32
@@ -782,6 +815,10 @@ def _load():
         "gcl_tcp_read": (i32, [vp, ctypes.POINTER(GclRdIn), ctypes.POINTER(GclRdOut), vp, vp,
                                ctypes.c_size_t, vp]),
         "gcl_tcp_read_host": (i32, [ctypes.POINTER(GclRdIn), ctypes.POINTER(GclRdOut), vp]),
+        "gcl_tcp_write_workspace": (i32, [u32, u64, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_write": (i32, [vp, ctypes.POINTER(GclWrIn), ctypes.POINTER(GclWrOut), vp, vp,
+                                ctypes.c_size_t, vp]),
+        "gcl_tcp_write_host": (i32, [ctypes.POINTER(GclWrIn), ctypes.POINTER(GclWrOut), vp]),
         "gcl_neigh_tbl_new": (vp, []),
         "gcl_neigh_tbl_free": (None, [vp]),
         "gcl_neigh_tbl_set": (i32, [vp, vp, u32]),
@@ -1923,6 +1960,71 @@ def tcp_read_workspace(nconn, nent, nvec=0, blocks=0):
     return need.value
 
 
+WR_OUT_WIDTH = {"desc": 32, "frame_off": 8, "seg_conn": 4, "txq_ent": 16, "txq_cold": 16, "src_off": 8, "len": 2,
+                "dst_off": 8, "item_conn": 4, "item_seg": 4}
+
+
+def _wr_structs(now, voff, iov, nvec, wr, conn, addr, nconn, seg_cap, item_cap, frame_base, frame_stride, frames_len,
+                blocks, out, counts):
+    """The two structs of gcl_tcp_write / gcl_tcp_write_host, sizes checked;
+    @out maps WR_OUT_FIELDS to buffers."""
+    if voff is not None and _nbytes(voff) < 4 * (nconn + 1):
+        raise ValueError("voff shorter than nconn + 1")
+    for arr, w in ((wr, 48), (conn, 48), (addr, 16), (out["out_conn"], 48)):
+        if arr is not None and _nbytes(arr) < w * nconn:
+            raise ValueError("per-connection array too small")
+    if voff is not None and iov is not None and _nbytes(iov) < 16 * nvec:
+        raise ValueError("iov shorter than nvec")
+    for f in WR_SEG_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < WR_OUT_WIDTH[f] * seg_cap:
+            raise ValueError(f"{f}: per-segment array shorter than seg_cap")
+    for f in WR_ITEM_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < WR_OUT_WIDTH[f] * item_cap:
+            raise ValueError(f"{f}: per-item array shorter than item_cap")
+    if out["totals"] is not None and _nbytes(out["totals"]) < 48:
+        raise ValueError("totals too small")
+    if counts is not None and _nbytes(counts) < 8 * WRC_NR:
+        raise ValueError("counts buffer too small")
+    win = GclWrIn(size=ctypes.sizeof(GclWrIn), blocks=blocks, now=now, voff=_ptr(voff), iov=_ptr(iov), nvec=nvec,
+                  wr=_ptr(wr), conn=_ptr(conn), addr=_ptr(addr), nconn=nconn, frame_stride=frame_stride,
+                  seg_cap=seg_cap, item_cap=item_cap, frame_base=frame_base, frames_len=frames_len)
+    return win, GclWrOut(**{f: _ptr(out[f]) for f in WR_OUT_FIELDS})
+
+
+def tcp_write_host(now, wr, conn, addr, seg_cap, item_cap, voff=None, iov=None, frame_stride=2048, frame_base=0,
+                   frames_len=0, nconn=None, nvec=None, blocks=0, out=None, counts=None):
+    """gcl_tcp_write_host: the rule of Classifier.tcp_write on the CPU over
+    numpy arrays.  @wr, @conn and @addr are TCP_WR_DTYPE, TCP_CONN_DTYPE and
+    TCP_ADDR_DTYPE arrays indexed by cookie; @voff an optional u32[nconn + 1]
+    CSR over the RD_IOV_DTYPE array @iov.  @out maps WR_OUT_FIELDS to arrays
+    (WR_CONN_OUT_DTYPE[nconn]; per segment TXH_DESC_DTYPE, u64, u32,
+    TXQ_ENT_DTYPE, TXQ_COLD_DTYPE, each @seg_cap long; per item u64, u16, u64,
+    u32, u32, each @item_cap long; totals u64[6]); the ones left out are
+    allocated.  @counts is a u64[WRC_NR], accumulated.  Returns the dict."""
+    nconn = len(wr) if nconn is None else nconn
+    nvec = (len(iov) if iov is not None else 0) if nvec is None else nvec
+    out = dict(out or {})
+    for f, dt, k in (("out_conn", WR_CONN_OUT_DTYPE, nconn), ("desc", TXH_DESC_DTYPE, seg_cap),
+                     ("frame_off", np.uint64, seg_cap), ("seg_conn", np.uint32, seg_cap),
+                     ("txq_ent", TXQ_ENT_DTYPE, seg_cap), ("txq_cold", TXQ_COLD_DTYPE, seg_cap),
+                     ("src_off", np.uint64, item_cap), ("len", np.uint16, item_cap), ("dst_off", np.uint64, item_cap),
+                     ("item_conn", np.uint32, item_cap), ("item_seg", np.uint32, item_cap), ("totals", np.uint64, 6)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    win, wout = _wr_structs(now, voff, iov, nvec, wr, conn, addr, nconn, seg_cap, item_cap, frame_base, frame_stride,
+                            frames_len, blocks, out, counts)
+    _check(lib.gcl_tcp_write_host(ctypes.byref(win), ctypes.byref(wout), _ptr(counts)), "gcl_tcp_write_host")
+    return out
+
+
+def tcp_write_workspace(nconn, nvec=0, blocks=0):
+    """gcl_tcp_write_workspace: bytes of device scratch a call over @nconn connections and @nvec
+    vectors takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_write_workspace(nconn, nvec, blocks, ctypes.byref(need)), "gcl_tcp_write_workspace")
+    return need.value
+
+
 def runtime_ip(r: int) -> int:
     return lib.gcl_runtime_ip(r)
 
@@ -2878,6 +2980,50 @@ class Classifier:
                 ws = self._rd_ws_buf = torch.empty(need, dtype=torch.uint8, device=out["totals"].device)
         _check(lib.gcl_tcp_read(self._ctx, ctypes.byref(rin), ctypes.byref(rout), _ptr(counts), _ptr(ws),
                                 _nbytes(ws), stream), "gcl_tcp_read")
+        return out
+
+    def tcp_write(self, now, wr, conn, addr, nconn, seg_cap, item_cap, voff=None, iov=None, nvec=0,
+                  frame_stride=2048, frame_base=0, frames_len=0, blocks=0, out=None, counts=None, workspace=None,
+                  stream=None):
+        """gcl_tcp_write: tcp_write / tcp_writev on one runtime's @nconn
+        connections at the clock reading @now (us) on the GPU, asynchronous:
+        whether each write goes ahead and what it returns, the segments it
+        sends with their retransmit-queue records, the copy items out of the
+        application's buffers and the tail it holds.  @wr, @conn and @addr are
+        device uint8[nconn, 48 / 48 / 16] (16-B aligned) of TCP_WR_DTYPE,
+        TCP_CONN_DTYPE and TCP_ADDR_DTYPE records; @voff (int32[nconn + 1]) and
+        @iov (uint8[nvec, 16], RD_IOV_DTYPE) the optional vectors.  @out maps
+        WR_OUT_FIELDS to device buffers; the ones left out are allocated on
+        @wr's device (out_conn uint8[nconn, 48]; desc uint8[seg_cap, 32],
+        frame_off int64, seg_conn int32, txq_ent and txq_cold uint8[seg_cap,
+        16]; src_off and dst_off int64, len int16, item_conn and item_seg
+        int32, item_cap long; totals int64[6]).  @counts is a device
+        u64[WRC_NR], accumulated.  The scratch is @workspace, or a torch tensor
+        the classifier keeps for this call alone.  Returns the dict: src_off,
+        len and dst_off are copy_batch's with totals[3] their n, desc and
+        frame_off tx_hdr's with totals[1] their m."""
+        import torch
+        dev = wr.device if hasattr(wr, "device") else None
+        out = dict(out or {})
+        sc, ic = max(seg_cap, 1), max(item_cap, 1)
+        for f, dt, shape in (("out_conn", torch.uint8, (max(nconn, 1), 48)), ("desc", torch.uint8, (sc, 32)),
+                             ("frame_off", torch.int64, (sc,)), ("seg_conn", torch.int32, (sc,)),
+                             ("txq_ent", torch.uint8, (sc, 16)), ("txq_cold", torch.uint8, (sc, 16)),
+                             ("src_off", torch.int64, (ic,)), ("len", torch.int16, (ic,)),
+                             ("dst_off", torch.int64, (ic,)), ("item_conn", torch.int32, (ic,)),
+                             ("item_seg", torch.int32, (ic,)), ("totals", torch.int64, (6,))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        nvec = nvec if voff is not None else 0
+        win, wout = _wr_structs(now, voff, iov, nvec, wr, conn, addr, nconn, seg_cap, item_cap, frame_base,
+                                frame_stride, frames_len, blocks, out, counts)
+        ws = workspace
+        if ws is None:
+            need, ws = tcp_write_workspace(nconn, nvec, blocks), getattr(self, "_wr_ws_buf", None)
+            if ws is None or ws.numel() < need or ws.device != out["totals"].device:
+                ws = self._wr_ws_buf = torch.empty(max(need, 16), dtype=torch.uint8, device=out["totals"].device)
+        _check(lib.gcl_tcp_write(self._ctx, ctypes.byref(win), ctypes.byref(wout), _ptr(counts), _ptr(ws),
+                                 _nbytes(ws), stream), "gcl_tcp_write")
         return out
 
     def copy_batch(self, src, src_off, length, n, dst, dst_off=None, dst_stride=0, tx_olflags=None,

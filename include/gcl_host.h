@@ -377,6 +377,22 @@ int gcl_tcp_txq_host(const struct gcl_txq_in *in, const struct gcl_txq_out *out,
 int gcl_tcp_read_host(const struct gcl_rd_in *in, const struct gcl_rd_out *out, uint64_t *counts);
 
 /*
+ * gcl_tcp_write_host - the rule of gcl_tcp_write (gclassify.h) on the CPU over
+ * host pointers, on one core: the wait of csrc/gcl_tcpwrite.h, then
+ * tcp_writev2's loop over the vectors (runtime/net/tcp.c:1405-1416) and
+ * tcp_tx_send's do ... while (tcp_out.c:329-380) over a simulated mbuf, taken
+ * literally, with (size_t)(fill - 20) < mss as the hold test.  A connection is
+ * run once to count and, when its segments, items and slots fit, once more to
+ * write.  The GPU reaches the same numbers through closed forms, so the twin
+ * and the kernels check each other.  The same out_conn, segments, items and
+ * totals byte for byte, the same counts and the same guarantee.  in->blocks is
+ * checked and otherwise ignored.  The time grows with the segments: a window
+ * of 2^31 - 1 bytes at mss 1 is that many passes.  0, or -EINVAL for what the
+ * call refuses (the ctx and the workspace apart).
+ */
+int gcl_tcp_write_host(const struct gcl_wr_in *in, const struct gcl_wr_out *out, uint64_t *counts);
+
+/*
  * gcl_host_deliver - consume @n verdicts in order.
  * @clients_by_id  dp.clients_by_id (iokernel/defs.h:386), @max_runtimes long
  * @clients        dp.clients[0..nr_clients) (broadcast order, rx.c:175)

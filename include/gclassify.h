@@ -3314,6 +3314,237 @@ int gcl_tcp_read_workspace(uint32_t nconn, uint64_t nent, uint64_t nvec, uint32_
 int gcl_tcp_read(struct gcl_ctx *ctx, const struct gcl_rd_in *in, const struct gcl_rd_out *out,
                  uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/*
+ * The socket writes of TCP: the step between the application and the transmit
+ * chain.  gcl_tx_seg cuts a write whose winlen and snd_nxt someone else worked
+ * out and always pushes; tcp_write3 / tcp_writev2 (runtime/net/tcp.c:
+ * tcp_write_wait :1259-1307, tcp_write_finish :1309-1349, :1362-1422) with
+ * tcp_tx_send (tcp_out.c:313-386) decide whether a write goes ahead at all,
+ * work the window out, gather the bytes of several iovecs into one segment and
+ * hold the unfinished tail in c->tx_pending.  gcl_tcp_write does that for
+ * every connection of one runtime at one instant, on a snapshot:
+ *
+ *   gcl_tcp_write -> gcl_copy_batch (src_off, len, dst_off) -> gcl_tx_hdr (desc,
+ *   frame_off) -> gcl_l4_csum GCL_L4_FILL ; (txq_ent, txq_cold appended to the
+ *   connection's queue) -> gcl_tcp_txq
+ *
+ * It works on every context and touches no table.
+ *
+ * The write of connection c is wr[c]: flags (GCL_WR_*), c->err, snd_mss, the
+ * ecn byte of its descriptors, tx_last_ack, the held c->tx_pending (pend_len
+ * bytes of payload in the frame at pend_frame_off, its seg_seq = snd_nxt -
+ * pend_len; pend_len 0: none) and, without GCL_WR_VEC, its buffer (src_off,
+ * len).  With GCL_WR_VEC the buffer is the vectors [voff[c], voff[c + 1]) of
+ * iov (struct gcl_rd_iov), and GCL_WR_NO_PARTIAL is ignored: tcp_write3 takes
+ * no vectors.  conn[c] gives snd_una, snd_wnd, snd_nxt, rcv_nxt and rcv_wnd,
+ * addr[c] the tuple and rcv_wscale, in->now the call's one clock reading.
+ *
+ * One connection; full(x) = wraps_lte(snd_una + snd_wnd, x):
+ *   1. no GCL_WR_WANT: status NONE, nothing changes.
+ *   2. status REFUSED, not written, when GCL_WR_VEC is set and there is no voff,
+ *      or its voff range is inverted or not inside [0, nvec], or holds more
+ *      than GCL_WR_MAX_IOV vectors, or the vectors named by the wanted vector
+ *      writes before it and its own are more than nvec (ranges that overlap:
+ *      never with a consistent CSR); when snd_mss == 0; when pend_len >
+ *      snd_mss; when 54 + snd_mss > frame_stride.
+ *   3. tcp_write_wait: not TX_CLOSED, and BELOW_EST or TX_EXCL or
+ *      full(snd_nxt): GCL_WRO_ZWND_ARM iff full(snd_nxt) and not ZERO_WND (the
+ *      host stores zero_wnd = true, zero_wnd_ts = now and runs the timer update
+ *      again); with NONBLOCK status AGAIN, ret -11, else status BLOCK, ret 0.
+ *      Nothing else changes.
+ *   4. Otherwise GCL_WRO_ZWND_CLEAR iff ZERO_WND was set (tcp.c:1285 runs before
+ *      the closed test).  TX_CLOSED: status CLOSED, ret = err ? -err : -32.
+ *      winlen = snd_una + snd_wnd - snd_nxt (mod 2^32; 1 .. 2^31 - 1 here).
+ *      Without VEC, with NO_PARTIAL and winlen < len: status NOSPC, ret -28.
+ *   5. The write goes ahead: GCL_WRO_ACKS_RESET (acks_delayed_cnt = 0,
+ *      ack_delayed = false) and GCL_WRO_TXWAKE.  Without VEC one
+ *      tcp_tx_send(min(len, winlen), push).  With VEC the vectors are walked
+ *      with the window that is left: stop at 0, skip an empty vector, send
+ *      min(iov_len, left) with push = (it is the last vector and iov_len <=
+ *      left).
+ *   6. tcp_tx_send(X, push) with h bytes held makes one pass per segment it
+ *      touches, at least one.  A held segment continues with min(rest, mss - h)
+ *      bytes (0 when it is full); otherwise a new segment takes min(rest, mss)
+ *      with seg_seq = snd_nxt and flags ACK.  snd_nxt advances.  With !push,
+ *      rest == 0 and (size_t)(fill - 20) < mss the segment is held: mbuf_length
+ *      does not hold the TCP header yet, so it is held iff fill >= 20; a tail of
+ *      1..19 bytes is sent short and without PSH (counted as SHORT), a tail of
+ *      exactly mss bytes is held.  Otherwise it is sent, with PSH iff push and
+ *      rest == 0.  X == 0 occurs for a plain write of len 0 alone: a held
+ *      segment is flushed with PSH, or an empty ACK|PSH segment is sent.
+ *   7. ret = the bytes taken = min(total, winlen); snd_nxt as the passes leave
+ *      it.  A vector write of no bytes (no vectors, or all of them empty) makes
+ *      no pass: ret 0, no segment and no item.
+ *   8. tcp_write_finish: GCL_WRO_ACK_TS iff rcv_nxt != tx_last_ack, where
+ *      tx_last_ack is rcv_nxt once a segment was sent (tcp_out.c:60);
+ *      GCL_WRO_POLLOUT_CLEAR iff full(snd_nxt after).  Status DONE.
+ *
+ * Every pass is one copy item: src_off = the vector's (buffer's) off + the
+ * bytes of it sent before, len (<= mss), dst_off = the segment's frame_off + 54
+ * + the bytes already in it, item_conn = c, item_seg = the index of the
+ * segment in the per-segment outputs, 0xFFFFFFFF for the one that is held when
+ * the call ends.  A pass that takes nothing gives an item of len 0.
+ *
+ * Every new segment, sent or held, takes the next slot frame_base + k *
+ * frame_stride, k counted over the call in connection and send order; the
+ * continued tx_pending keeps pend_frame_off and takes none.  Per sent segment,
+ * in connection order and then send order: desc (proto 6, the flags above,
+ * tcp_off 5, seq, ack = rcv_nxt, win = (rcv_wnd >> rcv_wscale) & 0xFFFF as on
+ * the wire, paylen, ecn), frame_off, seg_conn, txq_ent {seg_seq, seg_end =
+ * seg_seq + paylen, ts = now} and txq_cold {frame_off, tcp_flags, tcp_off 5,
+ * GCL_TXQE_INFLIGHT}: what the connection's queue of gcl_tcp_txq gains.  A sent
+ * segment implies tx_last_ack = rcv_nxt and tx_last_win = rcv_wnd for the host
+ * to store.
+ *
+ * Caps.  S_c, I_c and K_c are the segments, items and slots wanted by the
+ * connections before c that went ahead.  Connection c that goes ahead is
+ * status NOSPACE, ret -105 (-ENOBUFS), when S_c + its segments > seg_cap, I_c +
+ * its items > item_cap or, with frames_len != 0, (K_c + its slots) *
+ * frame_stride > frames_len - frame_base (no room at all below frame_base).
+ * It writes nothing and changes nothing: flags 0, snd_nxt and the pending
+ * words as they came.  The sums count those connections too and only grow, so
+ * the NOSPACE connections are a suffix of those that went ahead: no later
+ * connection is sent once one does not fit, not even a vector write of no
+ * bytes, which wants nothing.
+ *
+ * out_conn[c], every byte written: ret; snd_nxt; first_seg = min(S_c, seg_cap)
+ * and nseg, first_item = min(I_c, item_cap) and nitems (0 unless DONE);
+ * pend_len and pend_frame_off after the call (0 and 0 when a DONE write leaves
+ * nothing held); status; flags.  totals u64[6]:
+ * segments wanted, written, items wanted, written, slots used, the sum of the
+ * DONE connections' ret.
+ *
+ * @counts is a device u64[GCL_WRC_NR], ACCUMULATED, may be NULL: one slot per
+ * status (GCL_WRS_* is its index), SEGS written, PUSH (segments with PSH), HELD
+ * (DONE connections that leave a tx_pending), SHORT, ITEMS written and BYTES
+ * (totals[5]).
+ *
+ * Every pointer is a device pointer; each array is aligned to its element,
+ * conn, addr, wr, iov, out_conn, desc, txq_ent and txq_cold to 16 B.
+ * Asynchronous on @hip_stream, six launches ordered by the stream alone: the
+ * prefix sums of the vectors the writes name (two launches), one lane per
+ * connection walks its vectors (at most GCL_WR_MAX_IOV; the walk has a true
+ * serial dependency, a short tail resets the segment phase), the scan of the
+ * block sums, one lane per connection places it, and one lane per segment and
+ * per item emits, from the prefix sums and a search: nothing that grows with
+ * the bytes runs serially.  No block waits for another and no atomic hands
+ * out a position: atomics only add to counts and totals.  No allocation, no
+ * host synchronisation.  @workspace (device, 16-B aligned) need not be zeroed
+ * and may be reused by the next call on the same stream.  nconn == 0 still
+ * writes totals.
+ *
+ * Guarantee: no content of voff, iov, wr, conn or addr causes a read outside
+ * the given arrays, or a write outside the first seg_cap elements of the
+ * per-segment outputs, the first item_cap elements of the per-item outputs,
+ * out_conn[0, nconn), totals, counts and the workspace.  Garbage voff is
+ * included: decreasing values, or values past nvec.  Ranges that overlap are
+ * each read.  The call writes no frame: the offsets it emits are the
+ * caller's to bound (frames_len).
+ *
+ * What stays with the runtime: the connection lock and waitq_wait (BLOCK),
+ * tx_exclusive, the waitq_release, poll_clear, tcp_conn_ack and the fast
+ * retransmit of tcp_write_finish, storing the words back and appending the
+ * queue records.
+ *
+ * gcl_tcp_write_workspace - bytes of device scratch a call takes: 32 per
+ *   vector and 36 per connection plus a fixed part.  -EINVAL for a NULL
+ *   @bytes, nconn > 2^20, nvec > 2^31 or blocks > GCL_WR_MAX_BLOCKS.
+ * gcl_tcp_write - -EINVAL for a NULL ctx, in or out; a wrong in->size; nconn >
+ *   2^20; nvec (with voff), seg_cap or item_cap > 2^31; blocks >
+ *   GCL_WR_MAX_BLOCKS; frame_stride < 54 or > 2^20; a NULL totals; with nconn >
+ *   0 a NULL wr, conn, addr or out_conn; with voff and nvec > 0 a NULL iov
+ *   (without voff neither iov nor nvec is looked at); with nconn > 0 and
+ *   seg_cap > 0 a NULL per-segment output; with nconn > 0 and item_cap > 0 a
+ *   NULL per-item output; any given array that is not aligned to its element;
+ *   a NULL workspace, one that is not 16-B aligned or one smaller than
+ *   gcl_tcp_write_workspace says.  -EIO when a launch fails.
+ */
+/* gcl_tcp_wr.flags */
+#define GCL_WR_WANT        0x01  /* a write is issued on this connection */
+#define GCL_WR_VEC         0x02  /* tcp_writev2 over its voff range; else tcp_write3 over (src_off, len) */
+#define GCL_WR_NONBLOCK    0x04  /* the call's or c->nonblocking */
+#define GCL_WR_NO_PARTIAL  0x08  /* tcp_write3's no_partial_write */
+#define GCL_WR_TX_CLOSED   0x10  /* c->tx_closed */
+#define GCL_WR_TX_EXCL     0x20  /* c->tx_exclusive */
+#define GCL_WR_ZERO_WND    0x40  /* c->zero_wnd */
+#define GCL_WR_BELOW_EST   0x80  /* pcb.state < TCP_STATE_ESTABLISHED */
+/* gcl_wr_conn_out.status, and the first counter slots */
+#define GCL_WRS_NONE     0
+#define GCL_WRS_DONE     1
+#define GCL_WRS_AGAIN    2
+#define GCL_WRS_BLOCK    3
+#define GCL_WRS_CLOSED   4
+#define GCL_WRS_NOSPC    5   /* -ENOSPC: no_partial_write and the window is shorter */
+#define GCL_WRS_REFUSED  6
+#define GCL_WRS_NOSPACE  7   /* a cap: -ENOBUFS */
+/* gcl_wr_conn_out.flags */
+#define GCL_WRO_ZWND_ARM       0x01  /* zero_wnd = true, zero_wnd_ts = now, tcp_timer_update */
+#define GCL_WRO_ZWND_CLEAR     0x02  /* zero_wnd = false */
+#define GCL_WRO_ACKS_RESET     0x04  /* acks_delayed_cnt = 0, ack_delayed = false */
+#define GCL_WRO_TXWAKE         0x08  /* tx_exclusive = false, release tx_wq */
+#define GCL_WRO_ACK_TS         0x10  /* ack_ts = now; clear: ack_delayed = false */
+#define GCL_WRO_POLLOUT_CLEAR  0x20  /* poll_clear(&c->poll_src, POLLOUT) */
+#define GCL_WR_MAX_IOV    1024       /* vectors of one write */
+#define GCL_WR_MAX_BLOCKS 1024       /* the cap on in->blocks */
+#define GCL_WR_MAX_CONN   (1u << 20)
+#define GCL_WR_MAX_STRIDE (1u << 20)
+#define GCL_WR_SEG_HELD   0xFFFFFFFFu /* item_seg of the segment that stays in tx_pending */
+enum { GCL_WRC_SEGS = 8, GCL_WRC_PUSH, GCL_WRC_HELD, GCL_WRC_SHORT, GCL_WRC_ITEMS, GCL_WRC_BYTES, GCL_WRC_NR = 14 };
+struct gcl_tcp_wr {        /* 48 B, 16-B aligned, host order: one write and the words of the connection it reads */
+	uint64_t src_off;      /* without GCL_WR_VEC: the buffer */
+	uint32_t len;
+	uint32_t tx_last_ack;
+	uint64_t pend_frame_off; /* c->tx_pending: where its Ethernet header lies */
+	uint32_t pend_len;     /* its payload bytes; 0: none */
+	int32_t  err;          /* c->err */
+	uint16_t snd_mss;
+	uint8_t  ecn;          /* as gcl_txh_desc.ecn */
+	uint8_t  flags;        /* GCL_WR_* */
+	uint8_t  pad[12];
+};
+struct gcl_wr_conn_out {   /* 48 B, 16-B aligned */
+	int64_t  ret;
+	uint32_t snd_nxt;
+	uint32_t first_seg, nseg, first_item, nitems;
+	uint32_t pend_len;
+	uint64_t pend_frame_off;
+	uint8_t  status;       /* GCL_WRS_* */
+	uint8_t  flags;        /* GCL_WRO_* */
+	uint8_t  pad[6];       /* written as 0 */
+};
+struct gcl_wr_in {
+	uint32_t size, blocks;             /* sizeof(struct gcl_wr_in); blocks as in gcl_tick_in */
+	uint64_t now;                      /* us: the call's one clock reading */
+	const uint32_t *voff;              /* optional u32[nconn + 1] */
+	const struct gcl_rd_iov *iov;      /* [nvec] */
+	uint64_t nvec;                     /* <= 2^31; not looked at without voff */
+	const struct gcl_tcp_wr *wr;       /* [nconn] */
+	const struct gcl_tcp_conn *conn;   /* [nconn] */
+	const struct gcl_tcp_addr *addr;   /* [nconn] */
+	uint32_t nconn;                    /* <= 2^20 */
+	uint32_t frame_stride;             /* bytes, 54 .. 2^20 */
+	uint64_t seg_cap;                  /* <= 2^31: the length of every per-segment output array */
+	uint64_t item_cap;                 /* <= 2^31: the length of every per-item output array */
+	uint64_t frame_base;
+	uint64_t frames_len;               /* 0: no limit */
+};
+struct gcl_wr_out {                    /* device, aligned to their element */
+	struct gcl_wr_conn_out *out_conn;  /* [nconn] */
+	struct gcl_txh_desc *desc;         /* [seg_cap] */
+	uint64_t *frame_off;               /* [seg_cap] */
+	uint32_t *seg_conn;                /* [seg_cap] */
+	struct gcl_txq_ent *txq_ent;       /* [seg_cap] */
+	struct gcl_txq_cold *txq_cold;     /* [seg_cap] */
+	uint64_t *src_off;                 /* [item_cap] */
+	uint16_t *len;                     /* [item_cap] */
+	uint64_t *dst_off;                 /* [item_cap] */
+	uint32_t *item_conn, *item_seg;    /* [item_cap] */
+	uint64_t *totals;                  /* u64[6], required */
+};
+int gcl_tcp_write_workspace(uint32_t nconn, uint64_t nvec, uint32_t blocks, size_t *bytes);
+int gcl_tcp_write(struct gcl_ctx *ctx, const struct gcl_wr_in *in, const struct gcl_wr_out *out,
+                  uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
