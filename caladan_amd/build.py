@@ -28,11 +28,11 @@ SOURCES_HIP = ["gcl_ctx.hip", "gcl_batch.hip", "gcl_loop.hip", "gcl_xfer.hip", "
                "gcl_plan.hip", "gcl_pack.hip", "gcl_csum.hip", "gcl_copy.hip", "gcl_sock.hip", "gcl_l4.hip",
                "gcl_payload.hip", "gcl_txhdr.hip", "gcl_seg.hip", "gcl_tcprx.hip", "gcl_tcptmr.hip",
                "gcl_txq.hip", "gcl_tcpopen.hip", "gcl_udprx.hip", "gcl_tcpread.hip",
-               "gcl_tcpwrite.hip"]
+               "gcl_tcpwrite.hip", "gcl_tcpshut.hip"]
 SOURCES_C = ["gcl_host.c", "gcl_pcap.c", "gcl_sock.c", "gcl_neigh.c"]
 DEPS = ["gcl_device.h", "gcl_kern.h", "gcl_ctx.h", "gcl_sock.h", "gcl_pay.h", "gcl_neigh.h", "gcl_txh.h", "gcl_seg.h",
         "gcl_tcprx.h", "gcl_tcprxf.h", "gcl_tcprxo.h", "gcl_tcprxs.h", "gcl_tcptmr.h", "gcl_txq.h",
-        "gcl_tcpopen.h", "gcl_udprx.h", "gcl_tcpread.h", "gcl_tcpwrite.h", "../../include/gclassify.h",
+        "gcl_tcpopen.h", "gcl_udprx.h", "gcl_tcpread.h", "gcl_tcpwrite.h", "gcl_tcpshut.h", "../../include/gclassify.h",
         "../../include/gcl_host.h", "../../include/gcl_pcap.h"]
 SOURCE_GROUP = "gcl_group.hip"
 DEPS_GROUP = ["../../include/gclassify.h", "../../include/gcl_group.h"]
@@ -437,6 +437,23 @@ def build_sanitized_tcpwrite(out_dir=None):
     return exe
 
 
+def build_sanitized_tcpshut(out_dir=None):
+    """The same ASan + UBSan host build of csrc/gcl_host.c, linked into
+    tests/fuzz/tcpshut_fuzz.c: a stand-alone driver of gcl_tcp_shut_host
+    (tcp_shutdown, tcp_close and tcp_abort for a batch of connections on the
+    CPU, with the rule of csrc/gcl_tcpshut.h that the GPU kernels share) over
+    exactly sized heap arrays with garbage states, ops, how and caps.
+    Returns the driver's path."""
+    out_dir = out_dir or os.path.join(ROOT, "build", "sanitize")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "tcpshut_fuzz")
+    srcs = [os.path.join(ROOT, "tests", "fuzz", "tcpshut_fuzz.c"), os.path.join(CSRC, "gcl_host.c")]
+    if _stale(exe, srcs + [os.path.join(CSRC, d) for d in DEPS]):
+        _run(["gcc", "-std=gnu11", "-Wall", "-Wno-unused-parameter", *SANITIZE_FLAGS,
+              "-o", exe, *srcs, "-lm"])
+    return exe
+
+
 if __name__ == "__main__":
     if "--sanitize" in sys.argv:
         print(build_sanitized())
@@ -459,5 +476,6 @@ if __name__ == "__main__":
         print(build_sanitized_udprx())
         print(build_sanitized_tcpread())
         print(build_sanitized_tcpwrite())
+        print(build_sanitized_tcpshut())
     else:
         build(force="--force" in sys.argv, verbose_resources="--resources" in sys.argv)

@@ -18,6 +18,7 @@
 #include "gcl_tcpopen.h"
 #include "gcl_tcpread.h"
 #include "gcl_tcpwrite.h"
+#include "gcl_tcpshut.h"
 #include "gcl_tcptmr.h"
 #include "gcl_txq.h"
 #include "gcl_txh.h"
@@ -2269,6 +2270,73 @@ int gcl_tcp_write_host(const struct gcl_wr_in *in, const struct gcl_wr_out *out,
 	memcpy(out->totals, tot, sizeof(tot));
 	if (counts)
 		for (int i = 0; i < GCL_WRC_NR; i++)
+			counts[i] += cnt[i];
+	return 0;
+}
+
+/* The rule of gcl_tcp_shut (gclassify.h) on the CPU: gcl_shut_rule of
+ * gcl_tcpshut.h for every connection in turn, the count of wanted segments
+ * running. */
+int gcl_tcp_shut_host(const struct gcl_shut_in *in, const struct gcl_shut_out *out, uint64_t *counts)
+{
+	uint64_t cnt[GCL_SHUTC_NR] = {0}, W = 0;
+
+	if (!in || !out || in->size != sizeof(*in) ||
+	    ctl_refused(in->nconn, in->blocks, in->seg_cap, in->frame_stride, in->nconn, &out->seg, counts))
+		return -EINVAL;
+	if (in->nconn && (!in->shut || !in->tmr || !in->conn || !in->addr || !out->out_conn))
+		return -EINVAL;
+	if (in->nconn && in->seg_cap && (!out->txq_ent || !out->txq_cold))
+		return -EINVAL;
+	if (((uintptr_t)in->shut & 15) || ((uintptr_t)in->tmr & 15) || ((uintptr_t)in->conn & 15) ||
+	    ((uintptr_t)in->addr & 15) || ((uintptr_t)out->out_conn & 15) || ((uintptr_t)out->txq_ent & 15) ||
+	    ((uintptr_t)out->txq_cold & 15))
+		return -EINVAL;
+	const uint64_t cap = gcl_shut_cap(in->seg_cap, in->frames_len, in->frame_base, in->frame_stride);
+
+	for (uint32_t c = 0; c < in->nconn; c++) {
+		const struct gcl_tcp_conn *cn = &in->conn[c];
+		struct gcl_shut_one t;
+		struct gcl_shut_res r;
+		uint32_t m[16], s[4], o[12], first = 0, nseg = 0;
+
+		memcpy(m, &in->tmr[c], sizeof(m)); /* little-endian host */
+		memcpy(s, &in->shut[c], sizeof(s));
+		gcl_shut_load(m, s, cn->snd_nxt, &t);
+		gcl_shut_rule(&t, in->now, &r);
+		if (r.want != GCL_SHUT_WANT_NONE) {
+			if (W >= cap) {
+				gcl_shut_nospace(&t, &r);
+			} else {
+				const uint64_t off = in->frame_base + W * in->frame_stride;
+				uint32_t a[4], d[16];
+
+				memcpy(a, &in->addr[c], sizeof(a));
+				gcl_shut_seg_words(a, r.want, cn->snd_nxt, cn->rcv_nxt, cn->rcv_wnd, off, in->now, d);
+				memcpy(&out->seg.desc[W], d, 32);
+				memcpy(&out->txq_ent[W], d + 8, 16);
+				memcpy(&out->txq_cold[W], d + 12, 16);
+				out->seg.frame_off[W] = off;
+				out->seg.seg_conn[W] = c;
+				out->seg.seg_src[W] = c;
+				out->seg.seg_kind[W] = r.want == GCL_SHUT_WANT_FIN ? GCL_CTL_FIN : GCL_CTL_RST;
+				first = (uint32_t)W;
+				nseg = 1;
+				cnt[r.want == GCL_SHUT_WANT_FIN ? GCL_SHUTC_FIN : GCL_SHUTC_RST]++;
+			}
+			W++;
+		}
+		gcl_shut_conn_words(&r, first, nseg, o);
+		memcpy(&out->out_conn[c], o, sizeof(o));
+		cnt[r.status]++;
+		cnt[GCL_SHUTC_FAIL] += r.err != 0;
+		cnt[GCL_SHUTC_PUT] += r.nput;
+		cnt[GCL_SHUTC_WARN] += (r.flags & GCL_SHO_WARN) != 0;
+	}
+	out->seg.totals[0] = W;
+	out->seg.totals[1] = W < cap ? W : cap;
+	if (counts)
+		for (int i = 0; i < GCL_SHUTC_NR; i++)
 			counts[i] += cnt[i];
 	return 0;
 }

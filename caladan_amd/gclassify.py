@@ -243,6 +243,20 @@ TXQ_COLD_DTYPE = np.dtype([("frame_off", "<u8"), ("tcp_flags", "u1"), ("tcp_off"
                            ("pad", "u1", (5,))])
 TXQ_CONN_OUT_DTYPE = np.dtype([("head_ts", "<u8"), ("nacked", "<u4"), ("nretx", "<u4"), ("first", "<u4"),
                                ("flags", "u1"), ("pad", "u1", (11,))])
+# gcl_tcp_shut: the ops, the request's flags, the status byte (also the first counter slots), the
+# connection flags, the other counters, the caps, and struct gcl_tcp_shut and gcl_shut_conn_out
+SHUT_OP_NONE, SHUT_OP_SHUTDOWN, SHUT_OP_CLOSE, SHUT_OP_ABORT = range(4)
+SHUT_TX_CLOSED, SHUT_RX_CLOSED, SHUT_RX_EXCL = 0x01, 0x02, 0x04
+SHUTS_NONE, SHUTS_DONE, SHUTS_BLOCK, SHUTS_ABORT_WAIT, SHUTS_EINVAL, SHUTS_REFUSED, SHUTS_NOSPACE = range(7)
+(SHO_POLLHUP, SHO_TX_CLOSED_SET, SHO_TXWAKE, SHO_POLLRDHUP_IN, SHO_RX_CLOSED_SET, SHO_RXWAKE, SHO_DETACH_POLL,
+ SHO_FREE_TXQ, SHO_FREE_PEND, SHO_FREE_RXQ, SHO_FREE_OOO, SHO_WARN, SHO_POLLOUT) = (1 << i for i in range(13))
+SHUTC_FIN, SHUTC_RST, SHUTC_FAIL, SHUTC_PUT, SHUTC_WARN = range(7, 12)
+SHUTS_NR, SHUTC_NR, SHUT_MAX_BLOCKS, SHUT_MAX_CONN, SHUT_TILE, CTL_FIN = 7, 12, 1024, 1 << 20, 256, 5
+TCP_SHUT_DTYPE = np.dtype([("how", "<i4"), ("op", "u1"), ("flags", "u1"), ("pad", "u1", (10,))])
+SHUT_CONN_OUT_DTYPE = np.dtype([("next_timeout", "<u8"), ("txq_ts", "<u8"), ("ret", "<i4"), ("err", "<i4"),
+                                ("snd_nxt", "<u4"), ("first_seg", "<u4"), ("flags", "<u4"), ("status", "u1"),
+                                ("state", "u1"), ("tmr_flags", "u1"), ("nseg", "u1"), ("nput", "u1"),
+                                ("pad", "u1", (7,))])
 STAT_NAMES = ["RX_UNREGISTERED_MAC", "RX_UNICAST_FAIL", "RX_BROADCAST_FAIL",
               "RX_FLOW_TAG_MATCH", "RX_UNHANDLED", "RX_HASH_MISSING", "RX_PULLED"]
 
@@ -641,6 +655,24 @@ class GclWrOut(ctypes.Structure):
     _fields_ = [(f, ctypes.c_void_p) for f in WR_OUT_FIELDS]
 
 
+class GclShutIn(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("now", ctypes.c_uint64),
+                ("shut", ctypes.c_void_p), ("tmr", ctypes.c_void_p), ("conn", ctypes.c_void_p),
+                ("addr", ctypes.c_void_p), ("nconn", ctypes.c_uint32), ("frame_stride", ctypes.c_uint32),
+                ("seg_cap", ctypes.c_uint64), ("frame_base", ctypes.c_uint64), ("frames_len", ctypes.c_uint64)]
+
+
+SHUT_SEG_FIELDS = CTLSEG_SEG_FIELDS + ("txq_ent", "txq_cold")
+SHUT_OUT_FIELDS = ("out_conn",) + SHUT_SEG_FIELDS + ("totals",)
+
+
+class GclShutOut(ctypes.Structure):
+    _fields_ = [("out_conn", ctypes.c_void_p), ("seg", GclCtlsegOut), ("txq_ent", ctypes.c_void_p),
+                ("txq_cold", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(GclShutIn) == 80 and ctypes.sizeof(GclShutOut) == 72
+assert TCP_SHUT_DTYPE.itemsize == 16 and SHUT_CONN_OUT_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclWrIn) == 104 and ctypes.sizeof(GclWrOut) == 96
 assert TCP_WR_DTYPE.itemsize == 48 and WR_CONN_OUT_DTYPE.itemsize == 48
 assert ctypes.sizeof(GclRdIn) == 112 and ctypes.sizeof(GclRdOut) == 104
@@ -819,6 +851,10 @@ def _load():
         "gcl_tcp_write": (i32, [vp, ctypes.POINTER(GclWrIn), ctypes.POINTER(GclWrOut), vp, vp,
                                 ctypes.c_size_t, vp]),
         "gcl_tcp_write_host": (i32, [ctypes.POINTER(GclWrIn), ctypes.POINTER(GclWrOut), vp]),
+        "gcl_tcp_shut_workspace": (i32, [u32, u32, ctypes.POINTER(ctypes.c_size_t)]),
+        "gcl_tcp_shut": (i32, [vp, ctypes.POINTER(GclShutIn), ctypes.POINTER(GclShutOut), vp, vp,
+                               ctypes.c_size_t, vp]),
+        "gcl_tcp_shut_host": (i32, [ctypes.POINTER(GclShutIn), ctypes.POINTER(GclShutOut), vp]),
         "gcl_neigh_tbl_new": (vp, []),
         "gcl_neigh_tbl_free": (None, [vp]),
         "gcl_neigh_tbl_set": (i32, [vp, vp, u32]),
@@ -2017,6 +2053,60 @@ def tcp_write_host(now, wr, conn, addr, seg_cap, item_cap, voff=None, iov=None, 
     return out
 
 
+SHUT_OUT_WIDTH = dict(CTLSEG_OUT_WIDTH, txq_ent=16, txq_cold=16)
+
+
+def _shut_structs(now, shut, tmr, conn, addr, nconn, seg_cap, frame_base, frame_stride, frames_len, blocks, out,
+                  counts):
+    """The two structs of gcl_tcp_shut / gcl_tcp_shut_host, sizes checked; @out
+    maps SHUT_OUT_FIELDS to buffers."""
+    for arr, w in ((shut, 16), (tmr, 64), (conn, 48), (addr, 16), (out["out_conn"], 48)):
+        if arr is not None and _nbytes(arr) < w * nconn:
+            raise ValueError("per-connection array too small")
+    for f in SHUT_SEG_FIELDS:
+        if out[f] is not None and _nbytes(out[f]) < SHUT_OUT_WIDTH[f] * seg_cap:
+            raise ValueError(f"{f}: per-segment array shorter than seg_cap")
+    if out["totals"] is not None and _nbytes(out["totals"]) < 16:
+        raise ValueError("totals too small")
+    if counts is not None and _nbytes(counts) < 8 * SHUTC_NR:
+        raise ValueError("counts buffer too small")
+    sin = GclShutIn(size=ctypes.sizeof(GclShutIn), blocks=blocks, now=now, shut=_ptr(shut), tmr=_ptr(tmr),
+                    conn=_ptr(conn), addr=_ptr(addr), nconn=nconn, frame_stride=frame_stride, seg_cap=seg_cap,
+                    frame_base=frame_base, frames_len=frames_len)
+    seg = GclCtlsegOut(**{f: _ptr(out[f]) for f in CTLSEG_OUT_FIELDS})
+    return sin, GclShutOut(out_conn=_ptr(out["out_conn"]), seg=seg, txq_ent=_ptr(out["txq_ent"]),
+                           txq_cold=_ptr(out["txq_cold"]))
+
+
+def tcp_shut_host(now, shut, tmr, conn, addr, seg_cap, frame_stride=64, frame_base=0, frames_len=0, nconn=None,
+                  blocks=0, out=None, counts=None):
+    """gcl_tcp_shut_host: the rule of Classifier.tcp_shut on the CPU over numpy
+    arrays.  @shut, @tmr, @conn and @addr are TCP_SHUT_DTYPE, TCP_TMR_DTYPE,
+    TCP_CONN_DTYPE and TCP_ADDR_DTYPE arrays indexed by cookie.  @out maps
+    SHUT_OUT_FIELDS to arrays (SHUT_CONN_OUT_DTYPE[nconn]; per segment
+    TXH_DESC_DTYPE, u64, u32, u8, u32, TXQ_ENT_DTYPE, TXQ_COLD_DTYPE, each
+    @seg_cap long; totals u64[2]); the ones left out are allocated.  @counts is
+    a u64[SHUTC_NR], accumulated.  Returns the dict."""
+    nconn = len(shut) if nconn is None else nconn
+    out = dict(out or {})
+    for f, dt, k in (("out_conn", SHUT_CONN_OUT_DTYPE, nconn), ("txq_ent", TXQ_ENT_DTYPE, seg_cap),
+                     ("txq_cold", TXQ_COLD_DTYPE, seg_cap)):
+        if f not in out:
+            out[f] = np.zeros(max(k, 1), dtype=dt)
+    _ctlseg_host_arrays(out, seg_cap)
+    sin, sout = _shut_structs(now, shut, tmr, conn, addr, nconn, seg_cap, frame_base, frame_stride, frames_len,
+                              blocks, out, counts)
+    _check(lib.gcl_tcp_shut_host(ctypes.byref(sin), ctypes.byref(sout), _ptr(counts)), "gcl_tcp_shut_host")
+    return out
+
+
+def tcp_shut_workspace(nconn, blocks=0):
+    """gcl_tcp_shut_workspace: bytes of device scratch a call over @nconn connections takes."""
+    need = ctypes.c_size_t()
+    _check(lib.gcl_tcp_shut_workspace(nconn, blocks, ctypes.byref(need)), "gcl_tcp_shut_workspace")
+    return need.value
+
+
 def tcp_write_workspace(nconn, nvec=0, blocks=0):
     """gcl_tcp_write_workspace: bytes of device scratch a call over @nconn connections and @nvec
     vectors takes."""
@@ -3024,6 +3114,44 @@ class Classifier:
                 ws = self._wr_ws_buf = torch.empty(max(need, 16), dtype=torch.uint8, device=out["totals"].device)
         _check(lib.gcl_tcp_write(self._ctx, ctypes.byref(win), ctypes.byref(wout), _ptr(counts), _ptr(ws),
                                  _nbytes(ws), stream), "gcl_tcp_write")
+        return out
+
+    def tcp_shut(self, now, shut, tmr, conn, addr, nconn, seg_cap, frame_stride=64, frame_base=0, frames_len=0,
+                 blocks=0, out=None, counts=None, workspace=None, stream=None):
+        """gcl_tcp_shut: tcp_shutdown / tcp_close / tcp_abort on one runtime's
+        @nconn connections at the clock reading @now (us) on the GPU,
+        asynchronous: the state, timer words and flags each request leaves, and
+        the FIN and RST segments with the FINs' retransmit-queue records.
+        @shut, @tmr, @conn and @addr are device uint8[nconn, 16 / 64 / 48 / 16]
+        (16-B aligned) of TCP_SHUT_DTYPE, TCP_TMR_DTYPE, TCP_CONN_DTYPE and
+        TCP_ADDR_DTYPE records.  @out maps SHUT_OUT_FIELDS to device buffers;
+        the ones left out are allocated on @shut's device (out_conn
+        uint8[nconn, 48]; desc uint8[seg_cap, 32], frame_off int64, seg_conn
+        int32, seg_kind uint8, seg_src int32, txq_ent and txq_cold
+        uint8[seg_cap, 16]; totals int64[2]).  @counts is a device
+        u64[SHUTC_NR], accumulated.  The scratch is @workspace, or a torch
+        tensor the classifier keeps for this call alone.  Returns the dict:
+        desc and frame_off are tx_hdr's with totals[1] their m."""
+        import torch
+        dev = shut.device if hasattr(shut, "device") else None
+        out = dict(out or {})
+        sc = max(seg_cap, 1)
+        for f, dt, shape in (("out_conn", torch.uint8, (max(nconn, 1), 48)), ("desc", torch.uint8, (sc, 32)),
+                             ("frame_off", torch.int64, (sc,)), ("seg_conn", torch.int32, (sc,)),
+                             ("seg_kind", torch.uint8, (sc,)), ("seg_src", torch.int32, (sc,)),
+                             ("txq_ent", torch.uint8, (sc, 16)), ("txq_cold", torch.uint8, (sc, 16)),
+                             ("totals", torch.int64, (2,))):
+            if f not in out:
+                out[f] = torch.empty(shape, dtype=dt, device=dev)
+        sin, sout = _shut_structs(now, shut, tmr, conn, addr, nconn, seg_cap, frame_base, frame_stride, frames_len,
+                                  blocks, out, counts)
+        ws = workspace
+        if ws is None:
+            need, ws = tcp_shut_workspace(nconn, blocks), getattr(self, "_shut_ws_buf", None)
+            if ws is None or ws.numel() < need or ws.device != out["totals"].device:
+                ws = self._shut_ws_buf = torch.empty(max(need, 16), dtype=torch.uint8, device=out["totals"].device)
+        _check(lib.gcl_tcp_shut(self._ctx, ctypes.byref(sin), ctypes.byref(sout), _ptr(counts), _ptr(ws),
+                                _nbytes(ws), stream), "gcl_tcp_shut")
         return out
 
     def copy_batch(self, src, src_off, length, n, dst, dst_off=None, dst_stride=0, tx_olflags=None,

@@ -393,6 +393,16 @@ int gcl_tcp_read_host(const struct gcl_rd_in *in, const struct gcl_rd_out *out, 
 int gcl_tcp_write_host(const struct gcl_wr_in *in, const struct gcl_wr_out *out, uint64_t *counts);
 
 /*
+ * gcl_tcp_shut_host - the rule of gcl_tcp_shut (gclassify.h) on the CPU over
+ * host pointers, on one core: gcl_shut_rule of csrc/gcl_tcpshut.h for every
+ * connection in turn, the count of wanted segments running.  The same
+ * out_conn, segments, queue records and totals byte for byte, the same counts
+ * and the same guarantee.  in->blocks is checked and otherwise ignored.  0, or
+ * -EINVAL for what the call refuses (the ctx and the workspace apart).
+ */
+int gcl_tcp_shut_host(const struct gcl_shut_in *in, const struct gcl_shut_out *out, uint64_t *counts);
+
+/*
  * gcl_host_deliver - consume @n verdicts in order.
  * @clients_by_id  dp.clients_by_id (iokernel/defs.h:386), @max_runtimes long
  * @clients        dp.clients[0..nr_clients) (broadcast order, rx.c:175)

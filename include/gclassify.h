@@ -3545,6 +3545,214 @@ int gcl_tcp_write_workspace(uint32_t nconn, uint64_t nvec, uint32_t blocks, size
 int gcl_tcp_write(struct gcl_ctx *ctx, const struct gcl_wr_in *in, const struct gcl_wr_out *out,
                   uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/*
+ * The end of a TCP connection as the application asks for it: tcp_shutdown,
+ * tcp_close and tcp_abort (runtime/net/tcp.c:1555-1633, with
+ * tcp_conn_shutdown_tx :1504-1546, tcp_conn_shutdown_rx :1492-1502 and
+ * tcp_conn_fail :1453-1484) for every connection of one runtime at one clock
+ * reading, on a snapshot, with the FIN of tcp_tx_ctl(FIN | ACK)
+ * (tcp_out.c:264-295) and the RST of tcp_tx_raw_rst (:98-128):
+ *
+ *   gcl_tcp_shut -> gcl_tx_hdr (desc, frame_off) -> gcl_l4_csum GCL_L4_FILL ;
+ *   (txq_ent, txq_cold of a FIN appended to the connection's queue) ->
+ *   gcl_tcp_txq ; state, tmr_flags, next_timeout stored -> gcl_tcp_rx_states,
+ *   gcl_tcp_tick
+ *
+ * It works on every context and touches no table.
+ *
+ * The request of connection c is shut[c]: op (GCL_SHUT_OP_*), how (the raw
+ * argument of tcp_shutdown: 0 SHUT_RD, 1 SHUT_WR, 2 SHUT_RDWR; read for
+ * SHUTDOWN alone) and flags (c->tx_closed, c->rx_closed, c->rx_exclusive).
+ * tmr[c] gives state, GCL_TMR_LIVE, _TX_EXCLUSIVE (X below), _TXQ, _OOO,
+ * _ACK_DELAYED, _ZERO_WND and the timestamps; conn[c] snd_nxt, rcv_nxt and
+ * rcv_wnd; addr[c] the tuple and rcv_wscale; in->now the one clock reading.
+ *
+ * One connection, S its state:
+ *   1. op NONE, or LIVE clear: status NONE; out_conn[c] repeats the input
+ *      words, err 0, flags 0.  Otherwise an op above ABORT or S > 9: status
+ *      REFUSED, nothing changes.
+ *   2. SHUTDOWN with how not 0, 1 or 2: status EINVAL, ret -22, nothing changes
+ *      (tcp.c:1560).
+ *   3. The tx part, for SHUTDOWN with how 1 or 2 and for CLOSE, in the
+ *      reference's order:
+ *      a. TX_CLOSED: nothing (:1510).
+ *      b. S < ESTABLISHED: FAIL(103, ECONNABORTED) and one RST with seq =
+ *         snd_nxt (:1513-1517).  The reference does not wait for X here, and
+ *         with X the fail does not free the txq.
+ *      c. X: status BLOCK, ret 0, nothing changes; the rx part and CLOSE's put
+ *         do not run either: the reference sleeps here before them (:1519).
+ *      d. Otherwise one FIN|ACK: seq = snd_nxt, ack = rcv_nxt, win = (rcv_wnd >>
+ *         rcv_wscale) & 0xFFFF, tcp_flags 0x11, tcp_off 5, no payload, ecn 0.
+ *         snd_nxt + 1.  The queue gains {seg_seq, seg_end = seg_seq + 1, ts =
+ *         now} and {frame_off, 0x11, 5, GCL_TXQE_INFLIGHT}: GCL_TMR_TXQ is set
+ *         in tmr_flags, and txq_ts becomes now unless TXQ was set already (the
+ *         FIN is the new head).  ESTABLISHED -> FIN_WAIT1, CLOSE_WAIT ->
+ *         LAST_ACK, and tcp_conn_set_state's tcp_timer_update gives
+ *         next_timeout by rule 9 of gcl_tcp_tick on the new state, the new TXQ
+ *         and now.  Any other state is the reference's WARN(): the FIN is sent
+ *         all the same, state and next_timeout stay, GCL_SHO_WARN.  Then
+ *         POLLHUP, TX_CLOSED_SET and TXWAKE.  A sent FIN implies tx_last_ack =
+ *         rcv_nxt and tx_last_win = rcv_wnd for the host to store.
+ *   4. The rx part, for SHUTDOWN with how 0 or 2 and for CLOSE: unless
+ *      RX_CLOSED is set or a FAIL of 3b has set it, POLLRDHUP_IN, RX_CLOSED_SET
+ *      and RXWAKE.
+ *   5. CLOSE: DETACH_POLL (poll_src.set_fn = clear_fn = NULL) and one
+ *      tcp_conn_put.
+ *   6. ABORT: S == CLOSED is status DONE with nothing.  Otherwise FAIL(103);
+ *      with X status ABORT_WAIT: the fail's effects are reported and no RST is
+ *      emitted, since the reference sends it with the snd_nxt the writer
+ *      leaves; without X one RST with seq = snd_nxt.
+ *   7. FAIL(e) is tcp_conn_fail: err = e, state CLOSED; from S < ESTABLISHED
+ *      tcp_conn_set_state's GCL_SHO_POLLOUT; next_timeout by rule 9 on state
+ *      CLOSED and the input flags, since the timer update (:1459) runs before
+ *      the frees (:1471-1479): it still counts the txq head and the OOO term
+ *      and is not recomputed afterwards.  The rx part as in 4.  Without
+ *      TX_CLOSED: TX_CLOSED_SET, TXWAKE, POLLHUP.  Without X: FREE_TXQ,
+ *      FREE_PEND, and GCL_TMR_TXQ cleared in tmr_flags.  Without RX_EXCL:
+ *      FREE_RXQ.  FREE_OOO always, GCL_TMR_OOO cleared.  One put if S was not
+ *      CLOSED.
+ *   8. nput (0..2) counts the puts of 5 and 7.  status DONE unless said
+ *      otherwise; ret 0 in every status but EINVAL and NOSPACE.
+ * Not modelled: the interrupted wait of tcp_shutdown (-EINTR).  tx_pending is
+ * left as the reference leaves it: a FIN neither flushes nor frees it (its
+ * bytes are below snd_nxt already); only FREE_PEND frees it.
+ *
+ * Segments.  A connection wants at most one.  cap = seg_cap, or with
+ * frames_len != 0 min(seg_cap, (frames_len - frame_base) / frame_stride), 0
+ * when frames_len < frame_base: gcl_tcp_write's fit test.  Let W_c be the
+ * connections before c that want one, k = min(W_c, cap).  A connection that
+ * wants one with W_c >= cap is status NOSPACE, ret -105 (-ENOBUFS), nothing
+ * changed: tcp_tx_ctl's -ENOMEM path is not played out.  Those are a suffix of
+ * the wanting connections; one that wants none is never NOSPACE.  Otherwise
+ * its segment is segment k of the call: desc[k]; frame_off[k] = frame_base + k
+ * * frame_stride; seg_conn[k] = seg_src[k] = c; seg_kind[k] = GCL_CTL_FIN or
+ * GCL_CTL_RST (the descriptor gcl_tcp_rx_ctl writes for rst_seq = snd_nxt);
+ * txq_ent[k] and txq_cold[k] the records of 3d for a FIN, all-zero bytes for
+ * an RST.  totals[0] = segments wanted, totals[1] = min(wanted, cap), the m of
+ * gcl_tx_hdr.
+ *
+ * out_conn[c], every byte written: next_timeout, txq_ts, ret, err (0: c->err
+ * stays), snd_nxt, first_seg (k when nseg is 1, else 0), the flag word
+ * (GCL_SHO_*), status, state, tmr_flags (the input byte with TXQ and OOO as
+ * above), nseg (0 or 1), nput, and zero padding.
+ *
+ * @counts is a device u64[GCL_SHUTC_NR], ACCUMULATED, may be NULL: one slot
+ * per status (GCL_SHUTS_* is its index), FIN and RST segments written, FAIL
+ * (connections failed), PUT (the sum of nput) and WARN.
+ *
+ * Every pointer is a device pointer; each array is aligned to its element,
+ * shut, tmr, conn, addr, out_conn, desc, txq_ent and txq_cold to 16 B.
+ * Asynchronous on @hip_stream, three launches ordered by the stream alone: one
+ * lane per connection decides and writes out_conn, the per-block counts are
+ * scanned, and one lane per connection emits its own segment (or takes its
+ * decision back as NOSPACE).  No block waits for another and no atomic hands
+ * out a position: atomics only add to counts.  No allocation, no host
+ * synchronisation.  @workspace (device, 16-B aligned) need not be zeroed and
+ * may be reused by the next call on the same stream.  nconn == 0 still writes
+ * totals.
+ *
+ * Guarantee: no content of shut, tmr, conn or addr causes a read outside the
+ * given arrays, or a write outside the first seg_cap elements of the
+ * per-segment outputs, out_conn[0, nconn), totals, counts and the workspace.
+ *
+ * What stays with the runtime: the connection lock; the sleeps behind BLOCK
+ * and ABORT_WAIT (and calling again when the writer is done); the delayed RST
+ * of ABORT_WAIT, with the writer's snd_nxt; the actual frees (FREE_*); the
+ * wake-ups and poll_set (the flag word says which); the puts; storing state,
+ * err, snd_nxt, next_timeout, txq_ts and the flags back; appending the FIN's
+ * record to the queue.
+ *
+ * gcl_tcp_shut_workspace - bytes of device scratch a call takes: 4 per block
+ *   (in->blocks, or the cap GCL_SHUT_MAX_BLOCKS when blocks is 0) and 1 per
+ *   connection, each rounded up to 16.  -EINVAL for a NULL @bytes, nconn > 2^20
+ *   or blocks > GCL_SHUT_MAX_BLOCKS.
+ * gcl_tcp_shut - -EINVAL for a NULL ctx, in or out; a wrong in->size; nconn >
+ *   2^20; seg_cap > 2^31; blocks > GCL_SHUT_MAX_BLOCKS; frame_stride < 54; a
+ *   NULL totals; with nconn > 0 a NULL shut, tmr, conn, addr or out_conn; with
+ *   nconn > 0 and seg_cap > 0 a NULL per-segment output; any given array that
+ *   is not aligned to its element; a NULL workspace, one that is not 16-B
+ *   aligned or one smaller than gcl_tcp_shut_workspace says.  -EIO when a
+ *   launch fails.
+ */
+/* gcl_tcp_shut.op */
+#define GCL_SHUT_OP_NONE     0
+#define GCL_SHUT_OP_SHUTDOWN 1   /* tcp_shutdown(c, how) */
+#define GCL_SHUT_OP_CLOSE    2   /* tcp_close(c) */
+#define GCL_SHUT_OP_ABORT    3   /* tcp_abort(c) */
+/* gcl_tcp_shut.flags */
+#define GCL_SHUT_TX_CLOSED   0x01  /* c->tx_closed */
+#define GCL_SHUT_RX_CLOSED   0x02  /* c->rx_closed */
+#define GCL_SHUT_RX_EXCL     0x04  /* c->rx_exclusive */
+/* gcl_shut_conn_out.status, and the first counter slots */
+#define GCL_SHUTS_NONE       0
+#define GCL_SHUTS_DONE       1
+#define GCL_SHUTS_BLOCK      2   /* the writer is busy: wait on tx_wq, call again */
+#define GCL_SHUTS_ABORT_WAIT 3   /* failed; the RST waits for the writer */
+#define GCL_SHUTS_EINVAL     4
+#define GCL_SHUTS_REFUSED    5
+#define GCL_SHUTS_NOSPACE    6   /* a cap: -ENOBUFS */
+#define GCL_SHUTS_NR         7
+/* gcl_shut_conn_out.flags */
+#define GCL_SHO_POLLHUP        0x0001  /* poll_set(&c->poll_src, POLLHUP) */
+#define GCL_SHO_TX_CLOSED_SET  0x0002  /* c->tx_closed = true */
+#define GCL_SHO_TXWAKE         0x0004  /* waitq_release(&c->tx_wq) */
+#define GCL_SHO_POLLRDHUP_IN   0x0008  /* poll_set(&c->poll_src, POLLRDHUP | POLLIN) */
+#define GCL_SHO_RX_CLOSED_SET  0x0010  /* c->rx_closed = true */
+#define GCL_SHO_RXWAKE         0x0020  /* waitq_release(&c->rx_wq) */
+#define GCL_SHO_DETACH_POLL    0x0040  /* poll_src.set_fn = clear_fn = NULL */
+#define GCL_SHO_FREE_TXQ       0x0080  /* mbuf_list_free(&c->txq) */
+#define GCL_SHO_FREE_PEND      0x0100  /* mbuf_free(c->tx_pending), if any */
+#define GCL_SHO_FREE_RXQ       0x0200  /* mbuf_list_free(&c->rxq) */
+#define GCL_SHO_FREE_OOO       0x0400  /* mbuf_list_free(&c->rxq_ooo) */
+#define GCL_SHO_WARN           0x0800  /* a FIN from a state other than ESTABLISHED and CLOSE_WAIT */
+#define GCL_SHO_POLLOUT        0x1000  /* tcp_conn_set_state from below ESTABLISHED: release tx_wq, POLLOUT */
+#define GCL_CTL_FIN          5      /* seg_kind[k] beside GCL_CTL_ACK .. GCL_CTL_SYNACK */
+#define GCL_SHUT_MAX_BLOCKS 1024    /* the cap on in->blocks */
+#define GCL_SHUT_MAX_CONN (1u << 20)
+enum { GCL_SHUTC_FIN = 7, GCL_SHUTC_RST, GCL_SHUTC_FAIL, GCL_SHUTC_PUT, GCL_SHUTC_WARN, GCL_SHUTC_NR = 12 };
+struct gcl_tcp_shut {      /* 16 B, 16-B aligned, host order: what the application asks of one connection */
+	int32_t  how;          /* tcp_shutdown's argument as it came */
+	uint8_t  op;           /* GCL_SHUT_OP_* */
+	uint8_t  flags;        /* GCL_SHUT_* */
+	uint8_t  pad[10];
+};
+struct gcl_shut_conn_out { /* 48 B, 16-B aligned */
+	uint64_t next_timeout, txq_ts;
+	int32_t  ret;
+	int32_t  err;          /* 0: c->err stays */
+	uint32_t snd_nxt;
+	uint32_t first_seg;    /* the index of its segment when nseg is 1, else 0 */
+	uint32_t flags;        /* GCL_SHO_* */
+	uint8_t  status;       /* GCL_SHUTS_* */
+	uint8_t  state;        /* enum tcp state */
+	uint8_t  tmr_flags;    /* GCL_TMR_* */
+	uint8_t  nseg;
+	uint8_t  nput;
+	uint8_t  pad[7];       /* written as 0 */
+};
+struct gcl_shut_in {
+	uint32_t size, blocks;             /* sizeof(struct gcl_shut_in); blocks as in gcl_tick_in */
+	uint64_t now;                      /* us: the call's one clock reading */
+	const struct gcl_tcp_shut *shut;   /* [nconn] */
+	const struct gcl_tcp_tmr *tmr;     /* [nconn] */
+	const struct gcl_tcp_conn *conn;   /* [nconn] */
+	const struct gcl_tcp_addr *addr;   /* [nconn] */
+	uint32_t nconn;                    /* <= 2^20 */
+	uint32_t frame_stride;             /* bytes, >= GCL_CTL_MIN_STRIDE */
+	uint64_t seg_cap;                  /* <= 2^31: the length of every per-segment output array */
+	uint64_t frame_base;
+	uint64_t frames_len;               /* 0: no limit */
+};
+struct gcl_shut_out {                  /* device, aligned to their element */
+	struct gcl_shut_conn_out *out_conn; /* [nconn] */
+	struct gcl_ctlseg_out seg;         /* [seg_cap] each; totals u64[2]: wanted, written */
+	struct gcl_txq_ent *txq_ent;       /* [seg_cap] */
+	struct gcl_txq_cold *txq_cold;     /* [seg_cap] */
+};
+int gcl_tcp_shut_workspace(uint32_t nconn, uint32_t blocks, size_t *bytes);
+int gcl_tcp_shut(struct gcl_ctx *ctx, const struct gcl_shut_in *in, const struct gcl_shut_out *out,
+                 uint64_t *counts, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Library version string. */
 const char *gcl_version(void);
 
